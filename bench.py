@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """North-star benchmark: 2D SSM bootstrap filter (examples/2D_ssm.jl), particle-steps/s.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -24,6 +24,16 @@ move between ranks).
     visible devices is a refusal, never a one-GPU run.
 The line's `ranks` object carries what the communicator itself reports (ncclCommCount), the
 devices and the particles per shard.
+
+A plain run sets up, warms up, times the K steps and prints the line: `value` and
+`ms_per_step` (one bench step, in milliseconds) come from the timed region alone. `--full` adds
+what takes runs of its own after it: the per-kernel pass on HIP events (`breakdown_ms_per_run`,
+`roofline.dominant_kernel`) and the CPU baselines (`cpu_baseline`); without it those three are
+null. `--dump-outputs DIR` writes what the last timed step left for its caller, as
+DIR/<name>.npy in float64: a fixed, seeded sample of the particles' rows of every column (the
+history x_1..x_{T+1} among them) and of the log-weights, the sampled indices, and the log
+evidence. The same arguments give the same inputs and the same sample, so two builds can be
+compared file for file.
 
 Rank 0 prints ONE JSON line (metric/value/.../roofline/cpu_baseline). Everything else
 goes to stderr.
@@ -92,6 +102,36 @@ def refuse_on_mismatch(verdict):
         sys.exit(2)
 
 
+DUMP_BUDGET = 48 << 20      # bytes of --dump-outputs files (under the 64 MB a comparison reads)
+DUMP_PARTICLES = 16384      # sampled particles, fewer when the columns are many (a long --T)
+DUMP_SEED = 20240229        # of the sample's indices: fixed, so two runs dump the same rows
+
+
+def sample_outputs(ctx, ev, budget=DUMP_BUDGET):
+    """What a caller of the timed path holds after its last step, as name -> float64 array: the
+    rows of a fixed sample of particles (sorted indices, numpy Philox DUMP_SEED) of every
+    column ([dim, k] or [k]) and of the log-weights, the indices themselves, and the log
+    evidence. The sample shrinks until everything fits `budget` bytes."""
+    n = int(ctx.n)
+    cols = [(name, ctx.col_find(name)) for name in sorted(ctx.col_names())]
+    per_particle = 8 * (sum(ctx.col_dim(c) for _, c in cols) + 2)   # + log-weight and index
+    k = max(1, min(n, DUMP_PARTICLES, budget // per_particle))
+    idx = np.sort(np.random.Generator(np.random.Philox(DUMP_SEED)).choice(n, size=k, replace=False)).astype(np.int64)
+    out = {"col_" + name: np.asarray(ctx.col_gather_rows(c, idx), dtype=np.float64) for name, c in cols}
+    out["log_weights"] = np.asarray(ctx.weights_download(), dtype=np.float64)[idx]
+    out["sample_index"] = idx.astype(np.float64)
+    out["log_evidence"] = np.array([ev], dtype=np.float64)
+    return out
+
+
+def dump_outputs(directory, arrays):
+    d = pathlib.Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", a)
+    return sum(a.nbytes for a in arrays.values())
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -138,6 +178,11 @@ def parse():
     ap.add_argument("--watchdog", type=float, default=120.0)
     ap.add_argument("--statements", action="store_true")
     ap.add_argument("--eager-store", action="store_true")
+    # after the timed steps: the last step's outputs as DIR/<name>.npy (sample_outputs)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None)
+    # everything beside the headline figure that takes runs of its own: the per-kernel pass
+    # (breakdown_ms_per_run, roofline.dominant_kernel) and the CPU baselines (cpu_baseline)
+    ap.add_argument("--full", action="store_true")
     return ap.parse_args()
 
 
@@ -521,13 +566,16 @@ def main():
     st = ctx.get_state()
     ev = ctx.log_evidence()
     xst = ctx.debug_exact() if exact else None   # exact shards: block / window needs, re-runs, history traces
+    if args.dump_outputs and rank == 0:   # before any further run: the last timed step's state
+        nb = dump_outputs(args.dump_outputs, sample_outputs(ctx, ev))
+        log(f"bench: wrote the last step's outputs to {args.dump_outputs} ({nb / 1e6:.1f} MB)")
 
-    # per-kernel durations: HIP events recorded on the context stream around every launch of
-    # the same graph (a separate instrumented pass of `steps` runs); not available on exact
-    # shards (their eager, host-driven run is not instrumented)
+    # per-kernel durations (--full): HIP events recorded on the context stream around every
+    # launch of the same graph (a separate instrumented pass of `steps` runs); not available on
+    # exact shards (their eager, host-driven run is not instrumented)
     prop_ms = red_ms = rs_ms = fin_ms = tot_ms = 0.0
     nres = 0
-    if not exact and not args.statements and args.multi_shards <= 1 and not inproc:
+    if args.full and not exact and not args.statements and args.multi_shards <= 1 and not inproc:
         ctx.set_timing(True)
         inst_runs = max(1, min(args.steps, 5))
         one_run()  # capture the instrumented graph
@@ -564,7 +612,7 @@ def main():
     step_traffic = sj.get("bytes_per_particle_step") if sj and not args.statements else None
 
     cpu = None
-    if rank == 0 and G == 1 and not args.no_cpu_baseline:   # the baseline is an N=1 figure
+    if args.full and rank == 0 and G == 1 and not args.no_cpu_baseline:   # the baseline is an N=1 figure
         if scheme == abi.RESAMPLE_MULTINOMIAL:   # the MT port covers the strata (the reference's scheme)
             cpu = None
         else:
@@ -662,18 +710,19 @@ def main():
                          "unit": "GB/s", "frac": value / G * STEP_BYTES / 1e9 / HBM_PEAK_GBS,
                          "traffic": step_traffic, "algorithmic_bytes_per_particle_step": STEP_BYTES,
                          "definition": "whole step: particle-steps/s per GPU x 104 B / 8 TB/s (SURVEY.md 8d)",
-                         "dominant_kernel": None if args.statements else {
+                         "dominant_kernel": None if args.statements or not args.full else {
                              "kernel": "k_ssm2d_prop (propagate+observe+max)", "achieved": prop_gbs,
                              "peak": HBM_PEAK_GBS, "unit": "GB/s",
                              "frac": (prop_gbs / HBM_PEAK_GBS) if prop_gbs else None, "traffic": traffic,
                              "algorithmic_bytes_per_run": prop_bytes,
                              "avg_launch_us": prop_ms * 1e3 / T if prop_ms > 0 else None}},
             "cpu_baseline": cpu,
-            "breakdown_ms_per_run": None if exact or args.statements else {
+            "breakdown_ms_per_run": None if exact or args.statements or not args.full else {
                 "propagate": prop_ms, "weight_stats": red_ms, "scan_ancestors": rs_ms,
                 "finalize_traceback": fin_ms, "instrumented_total": tot_ms,
                 "resamples_per_run": nres, "forced_every_step": forced},
             "log_evidence_last": ev,
+            "full": args.full,
             "ranks": ranks,
         }
         if xst is not None:

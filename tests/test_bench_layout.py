@@ -1,6 +1,8 @@
 """bench.py's `--gpus N` contract: the line measures N GPUs or the run
-refuses. CPU only: the layout planner with stand-in device counts, and the real script on this
-GPU-less container, which must exit 2 with the reason rather than measure one GPU."""
+refuses. On the CPU: the layout planner with stand-in device counts, and the real script on
+a host without a GPU, which must exit 2 with the reason rather than measure one GPU; the
+sample that `--dump-outputs` writes, over a stand-in store. On the GPU (`-m gpu`): a plain
+run of the real script is lean and dumps the same outputs twice, `--full` adds the rest."""
 import os
 import pathlib
 import subprocess
@@ -146,3 +148,89 @@ def test_self_check_mismatch_refuses_the_line():
     assert not v["exact_vs_1gpu"] and not v["evidence_equal"]
     with pytest.raises(SystemExit):
         bench.refuse_on_mismatch(v)
+
+
+class _FakeStore(_FakeCtx):
+    """_FakeCtx plus n / col_dim / col_gather_rows: what bench.sample_outputs reads."""
+    def __init__(self, cols, w):
+        super().__init__(cols, w)
+        self.n = len(w)
+
+    def col_dim(self, c):
+        return 1 if self.cols[c].ndim == 1 else self.cols[c].shape[0]
+
+    def col_gather_rows(self, c, idx):
+        return self.cols[c][..., idx]
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs: the same seeded sample of particles every time, every array float64 and
+    the rows of the population at the sampled indices, the files within the byte budget."""
+    import numpy as np
+    cols, w = _population(n=5000, seed=3)
+    a = bench.sample_outputs(_FakeStore(cols, w), -12.5)
+    b = bench.sample_outputs(_FakeStore(cols, w), -12.5)
+    assert sorted(a) == ["col_a", "col_v", "col_x_1", "log_evidence", "log_weights", "sample_index"]
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    idx = a["sample_index"].astype(np.int64)
+    assert len(idx) == 5000                            # fewer particles than the sample: all of them
+    assert np.array_equal(idx, np.arange(5000))
+    small = bench.sample_outputs(_FakeStore(cols, w), -12.5, budget=7 * 8 * 100)   # 5 column rows + w + index
+    idx = small["sample_index"].astype(np.int64)
+    assert len(idx) == 100 and np.all(np.diff(idx) > 0) and idx[-1] < 5000
+    assert np.array_equal(small["col_x_1"], cols["x_1"][:, idx])
+    assert np.array_equal(small["col_a"], cols["a"][idx])
+    assert np.array_equal(small["log_weights"], w[idx])
+    assert small["log_evidence"].tolist() == [-12.5]
+    nbytes = bench.dump_outputs(tmp_path / "out", small)
+    assert nbytes <= 7 * 8 * 100 + 8
+    files = sorted(p.name for p in (tmp_path / "out").iterdir())
+    assert files == sorted(k + ".npy" for k in small)
+    assert np.array_equal(np.load(tmp_path / "out" / "col_v.npy"), small["col_v"])
+
+
+def _bench_line(args):
+    import json
+    r = run_bench(["--gpus", "1", "--particles", "20000", "--T", "12", *args], {})
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = r.stdout.strip().splitlines()
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_same_outputs_twice(tmp_path, gpu_available):
+    """A plain run times its steps and nothing else (no per-kernel pass, no CPU legs); with
+    --dump-outputs two runs of the same arguments write the same files, bit for bit."""
+    import numpy as np
+    args = ["--steps", "3", "--warmup", "1"]
+    line = _bench_line([*args, "--dump-outputs", str(tmp_path / "a")])
+    _bench_line([*args, "--dump-outputs", str(tmp_path / "b")])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["full"] is False
+    assert line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(20000 * 12 / (line["ms_per_step"] * 1e-3), rel=1e-9)
+    assert line["cpu_baseline"] is None and line["breakdown_ms_per_run"] is None
+    assert line["roofline"]["dominant_kernel"] is None and line["roofline"]["frac"] > 0
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(p.name for p in (tmp_path / "b").iterdir())
+    assert {"log_weights.npy", "log_evidence.npy", "sample_index.npy", "col_x_1.npy", "col_x_13.npy"} <= set(names)
+    total = 0
+    for nm in names:
+        a, b = np.load(tmp_path / "a" / nm), np.load(tmp_path / "b" / nm)
+        assert a.dtype == np.float64 and np.array_equal(a, b), nm
+        assert np.all(np.isfinite(a)), nm
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.load(tmp_path / "a" / "col_x_13.npy").shape == (2, bench.DUMP_PARTICLES)
+    assert np.load(tmp_path / "a" / "log_evidence.npy")[0] == line["log_evidence_last"]
+
+
+@pytest.mark.gpu
+def test_full_run_adds_the_kernel_breakdown_and_the_cpu_legs(gpu_available):
+    line = _bench_line(["--steps", "2", "--warmup", "1", "--full", "--cpu-particles", "20000", "--cpu-T", "12",
+                        "--cpu-1t-particles", "20000"])
+    assert line["full"] is True and line["ms_per_step"] > 0
+    assert line["breakdown_ms_per_run"]["propagate"] > 0
+    assert line["roofline"]["dominant_kernel"]["achieved"] > 0
+    assert line["cpu_baseline"]["value"] > 0 and line["cpu_baseline"]["gpu_over_cpu"] > 0

@@ -83,7 +83,7 @@ tests)   # [pytest args]: files / -k; the whole suite by default
   step 1100 $O/pytest_gpu.log python -u -m pytest -q -m gpu -x --timeout 600 --timeout-method thread "$@"
   tail -1 $O/pytest_gpu.log ;;
 evidence)   # the round's measurements without the test suite (run `tests` before it)
-  timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+  timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
   line $O/bench.json bench
   timeout -k 10 400 python bench.py --no-cpu-baseline --statements > $O/bench_statements.json 2> $O/bench_statements.err || { tail -20 $O/bench_statements.err; exit 1; }
   line $O/bench_statements.json statements
@@ -95,13 +95,13 @@ round)
   tail -1 $O/pytest_gpu.log
   step 300 $O/smoke.log python -c "import __graft_entry__ as g; g.smoke()"
   echo smoke ok
-  timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+  timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
   line $O/bench.json bench
   timeout -k 10 400 python bench.py --no-cpu-baseline --statements > $O/bench_statements.json 2> $O/bench_statements.err || { tail -20 $O/bench_statements.err; exit 1; }
   line $O/bench_statements.json statements
   prof_passes ;;
 big)    # the beyond-MALL line: 8M particles, its kernel stats and PMC step bytes
-  timeout -k 10 400 python bench.py --particles 8000000 --steps 40 --warmup 3 > $O/bench8m.json 2> $O/bench8m.err || { tail -20 $O/bench8m.err; exit 1; }
+  timeout -k 10 400 python bench.py --full --particles 8000000 --steps 40 --warmup 3 > $O/bench8m.json 2> $O/bench8m.err || { tail -20 $O/bench8m.err; exit 1; }
   line $O/bench8m.json bench-8M
   step 400 $O/stats8m.log rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats8m -o run -- python bench.py --no-cpu-baseline --particles 8000000 --steps 10 --warmup 2
   stats_table $O/stats8m/run_kernel_stats.csv 6
@@ -113,7 +113,7 @@ big)    # the beyond-MALL line: 8M particles, its kernel stats and P
   cat $O/pmc_step_bytes8m.json ;;
 prof)   # the round's profile passes alone (kernel stats, FETCH_SIZE / WRITE_SIZE)
   prof_passes ;;
-bench)  timeout -k 10 400 python bench.py "$@" > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+bench)  timeout -k 10 400 python bench.py --full "$@" > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
   line $O/bench.json bench
   step 400 $O/stats.log rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- python bench.py --no-cpu-baseline --steps 20 --warmup 2 "$@"
   stats_table $O/stats/run_kernel_stats.csv 8 ;;
