@@ -398,6 +398,26 @@ int wsmc_ssm2d_run(wsmc_ctx* ctx, const double* obs /* T x 2, row-major */, int3
                    const double* x0, const double* v0, double q_var, double r_var,
                    double ess_perc_min, int32_t scheme, int32_t keep_history,
                    double* log_evidence_out);
+/* benchmarks/ssm/WeightedSampling/lgssm1d.jl:18-24 as one call:
+ *   x ~ Normal(0, x0_std); for y in data: x ~ Normal(a*x, q); y => Normal(x, r); end
+ * (+ the auto-inserted Resample after every ~ / =>). Produces the same column `x`, weights,
+ * ancestors, state fields, score tape and RNG stream positions as issuing those statements one
+ * by one (models.lgssm1d_statements). Synchronous: on return the run is complete and folded in.
+ * One unsharded context of at most wsmc_debug_lgssm's cap particles, holding no column but a
+ * dim-1 `x`, with a stratified or systematic scheme runs on one persistent workgroup (the
+ * population in LDS, the steps looped on the device, a launch per segment of steps); everything
+ * else issues the statements themselves inside the library.
+ * ess_trace_out (may be NULL): T doubles, the ESS% each step's post-Observe Resample computed
+ * (what a waited wsmc_resample returns in ess_perc_out; NaN kept).
+ * WSMC_EARG: null data, T < 1, q <= 0, r <= 0, x0_std <= 0, an unknown scheme. */
+int wsmc_lgssm1d_run(wsmc_ctx* ctx, const double* data, int32_t T, double a, double q, double r,
+                     double x0_std, double ess_perc_min, int32_t scheme,
+                     double* log_evidence_out, double* ess_trace_out);
+/* segment_steps > 0 sets the steps per launch, 0 restores the default, < 0 leaves it; stats_out[6]
+ * (may be NULL) = the largest N the persistent kernel takes, runs it took, runs that went through
+ * the statement route, segments launched (cumulative per context), then the last run's host
+ * bookkeeping time (tape and state, done while the device runs) and whole-call time, microseconds. */
+int wsmc_debug_lgssm(wsmc_ctx* ctx, int32_t segment_steps, int64_t* stats_out);
 /* per-kernel timing of the last fused run (HIP events on the ctx stream), ms */
 typedef struct {
     double total_ms;            /* whole run, first kernel to last                       */

@@ -6,6 +6,12 @@ check"): the 1D linear-Gaussian SSM of benchmarks/ssm/WeightedSampl
              step: the generic drop-in path a `@model` lowers to), N = 1e6, against the
              reference's published run! wall at the same N and T (22.170888 s,
              benchmarks/ssm/results/grid_results.csv:14, one Julia thread, hardware unstated)
+  gpu_small  the same statement operators at N = 1e3 (gpu_small=N: another N)
+  gpu_fused  wsmc_lgssm1d_run, one call a run: T = 1e3 at N = 1e3 (the persistent workgroup;
+             published 0.092459 s, grid_results.csv default point) and at N = 1e6 (past the
+             kernel's cap: the statements inside the library)
+  gpu_fused_long  wsmc_lgssm1d_run at T = 1e6, N = 1e3 (published 19.09 s, grid_results.csv:26);
+             gpu_fused_long=T runs another T (sizing the long run's time limit)
   cpu_1t     oracle/wsmc_port_fast.c (the reference's algorithm at the reference's speed:
              xoshiro256++, ziggurat, libm, f64 icdf) on 1 thread, N = 1e5 — the fairness check
              against the published 5.30e7 (single update, N = 1e5, grid_results.csv:46) and
@@ -54,6 +60,36 @@ def gpu(N=1_000_000, T=1000, reps=2, wait=False):
             "speedup_vs_published": PUBLISHED_RUN_S / best}
 
 
+PUBLISHED_FUSED_S = {(1000, 1000): 0.092459, (1_000_000, 1000): PUBLISHED_RUN_S,
+                     (1000, 1_000_000): 19.09}   # grid_results.csv: default, high particle, long time
+
+
+def gpu_fused(N, T, reps=2):
+    """wsmc_lgssm1d_run (one call a run): the persistent workgroup at N within its cap, the
+    statements inside the library above it. Timed around the call, which returns synchronised."""
+    data = models.lgssm1d_data(T)
+    best, ev, st, nres = float("inf"), None, None, 0
+    for _ in range(reps + 1):           # the first run is the warm-up
+        ctx = wsmc.Context(N, seed=42)
+        ctx.sync()
+        t0 = time.perf_counter()
+        ctx.lgssm1d_run(data, ess_perc_min=1.0, want_evidence=False)
+        dt = time.perf_counter() - t0
+        if dt < best:
+            best, st = dt, ctx.lgssm_stats()
+        ev = ctx.log_evidence()
+        nres = ctx.get_state()["n_resamples"]
+        ctx.close()
+    pub = PUBLISHED_FUSED_S.get((N, T))
+    out = {"leg": "gpu fused, " + ("persistent workgroup" if st["persistent_runs"] else "statement route"),
+           "N": N, "T": T, "seconds_per_run": best, "particle_steps_per_s": N * T / best,
+           "host_bookkeeping_s": st["bookkeeping_s"], "segments": st["segments"], "resamples": nres,
+           "log_evidence": ev}
+    if pub:
+        out.update(reference_published_s=pub, speedup_vs_published=pub / best)
+    return out
+
+
 def cpu(N, T, nth, reps=1):
     import oracle  # test infrastructure: a CPU baseline leg
     data = models.lgssm1d_data(T)
@@ -71,8 +107,16 @@ def cpu(N, T, nth, reps=1):
 if __name__ == "__main__":
     which = sys.argv[1:] or ["gpu", "gpu_wait", "cpu_1t", "cpu_all"]
     for w in which:
+        w, _, arg = w.partition("=")     # gpu_small=N, gpu_fused_long=T: another size (sizing a run's timeout)
         if w == "gpu":
             r = gpu()
+        elif w == "gpu_small":
+            r = gpu(N=int(arg or 1000))
+        elif w == "gpu_fused":
+            print(json.dumps(gpu_fused(1000, 1000)), flush=True)
+            r = gpu_fused(1_000_000, 1000)
+        elif w == "gpu_fused_long":
+            r = gpu_fused(1000, int(arg or 1_000_000), reps=1 if arg else 0)
         elif w == "gpu_wait":
             r = gpu(wait=True)
         elif w == "cpu_1t":

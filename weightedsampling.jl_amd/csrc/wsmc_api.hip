@@ -765,7 +765,8 @@ int wsmc_destroy(wsmc_ctx* c) {
     void* bufs[] = {c->dec_always, c->xchg, c->scache, c->scache_back, c->w, c->anc, c->tmp, c->tilep, c->tileOff, c->taskOff, c->taskTile, c->mslots, c->qbuf, c->cdf, c->tilepart, c->rec, c->dec, c->mom, c->dflag, c->ucount, c->wslots[0], c->wslots[1],
                     c->d_colptr, c->run_params, c->d_tape, c->run_max, c->run_rec, c->run_dec, c->anc_log, c->obs_buf, c->run_grp, c->run_rg, c->run_nfix, c->run_w0,
                     c->vscratch, c->xscratch, c->xp, c->comb, c->anc_out, c->xbuf, c->d_comp, c->d_ctape, c->d_prog, c->rs_grp[0], c->rs_grp[1], c->rs_qs,
-                    c->xpairs, c->xnb, c->xwin, c->xstat, c->w_save, c->xms, c->xanc, c->xlines, c->xpeer};
+                    c->xpairs, c->xnb, c->xwin, c->xstat, c->w_save, c->xms, c->xanc, c->xlines, c->xpeer,
+                    c->lg_data, c->lg_trace, c->lg_rec};
     for (void* p : bufs)
         if (p) (void)hipFree(p);
     for (double* p : c->xrun)
@@ -5033,6 +5034,197 @@ int wsmc_debug_kernel_bench(wsmc_ctx* c, int32_t kernel, int32_t mode, int32_t i
     if (stream4) (void)hipFree(stream4);
     WSMC_HIP(e);
     *avg_us = 1e3 * ms / iters;
+    return WSMC_OK;
+}
+
+// ---- fused 1D LGSSM run (csrc/wsmc_lgssm.hip) ------------------------------------------------
+// Normal(c0 + coef * col, sigma) as wsmc.dsl's Normal(...).dist builds it (col < 0: Normal(0, sigma))
+static wsmc_dist lg_normal(int32_t col, double coef, double sigma) {
+    wsmc_dist d;
+    std::memset(&d, 0, sizeof(d));
+    d.family = WSMC_FAM_NORMAL;
+    d.mean_fn = WSMC_MEAN_AFFINE;
+    d.dim = 1;
+    for (int k = 0; k < 4; ++k) d.mu[k].col[0] = d.mu[k].col[1] = -1;
+    if (col >= 0) {
+        d.mu[0].col[0] = col;
+        d.mu[0].coef[0] = coef;
+    }
+    d.scale.c0 = sigma;
+    d.scale.col[0] = d.scale.col[1] = -1;
+    return d;
+}
+static void lg_const4(double y, wsmc_operand* x) {
+    for (int k = 0; k < 4; ++k) {
+        std::memset(&x[k], 0, sizeof(wsmc_operand));
+        x[k].c0 = y;
+        x[k].col[0] = x[k].col[1] = -1;
+    }
+}
+// the statement route: models.lgssm1d_statements as a loop over the operators (any handle, any N,
+// any scheme). The Resamples stay asynchronous unless the ESS trace is wanted.
+static int lgssm_statements(wsmc_ctx* c, const double* data, int32_t T, double a, double q, double r, double x0_std,
+                            double ess_min, int32_t scheme, double* ess_trace) {
+    int rc;
+    int32_t cx = -1;
+    if ((rc = wsmc_col_create(c, "x", 1, &cx))) return rc;
+    const wsmc_dist prior = lg_normal(-1, 0.0, x0_std), trans = lg_normal(cx, a, q), lik = lg_normal(cx, 1.0, r);
+    if ((rc = wsmc_sample(c, cx, &prior))) return rc;
+    if ((rc = wsmc_resample(c, ess_min, scheme, nullptr, nullptr))) return rc;
+    for (int32_t t = 0; t < T; ++t) {
+        wsmc_operand y[4];
+        lg_const4(data[t], y);
+        int32_t rs = 0;
+        if ((rc = wsmc_sample(c, cx, &trans))) return rc;
+        if ((rc = wsmc_resample(c, ess_min, scheme, nullptr, nullptr))) return rc;
+        if ((rc = wsmc_observe(c, &lik, y))) return rc;
+        if ((rc = wsmc_resample(c, ess_min, scheme, ess_trace ? &rs : nullptr, ess_trace ? ess_trace + t : nullptr)))
+            return rc;
+    }
+    return wsmc_sync(c);
+}
+
+int wsmc_lgssm1d_run(wsmc_ctx* c, const double* data, int32_t T, double a, double q, double r, double x0_std,
+                     double ess_min, int32_t scheme, double* log_evidence_out, double* ess_trace_out) {
+    if (!c) return fail(WSMC_EARG, "null context");
+    if (!data || T < 1) return fail(WSMC_EARG, "bad arguments");
+    if (!(q > 0) || !(r > 0) || !(x0_std > 0)) return fail(WSMC_EARG, "standard deviations must be positive");
+    if (!valid_scheme(scheme)) return fail(WSMC_EARG, "unknown resampling scheme");
+    using clk = std::chrono::steady_clock;
+    auto us = [](clk::time_point t0, clk::time_point t1) {
+        return (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count();
+    };
+    const auto t_in = clk::now();
+    wsmc_ctx* sc = c->multi ? multi_first(c) : c;   // the counters' holder
+    // the persistent workgroup: one unsharded context, N within the cap, a stratified / systematic
+    // scheme, no column but a dim-1 `x`, and the first (auto-inserted) Resample a no-op
+    bool persistent = !c->multi && !is_sharded(c) && c->N <= kLgCap && scheme != WSMC_RESAMPLE_MULTINOMIAL &&
+                      !c->weights_changed && c->cols.size() <= 1;
+    if (persistent && c->cols.size() == 1) persistent = c->cols[0].name == "x" && c->cols[0].dim == 1;
+    if (!persistent) {
+        int rc = lgssm_statements(c, data, T, a, q, r, x0_std, ess_min, scheme, ess_trace_out);
+        if (rc) return rc;
+        sc->lg_stmt_runs += 1;
+        sc->lg_book_us = 0;
+        if (log_evidence_out && (rc = wsmc_log_evidence(c, log_evidence_out))) return rc;
+        sc->lg_wall_us = us(t_in, clk::now());
+        return WSMC_OK;
+    }
+    CHECK_CTX(c);   // an asynchronous run, the open statement batch, unstored Samples, a pending reset
+    if (int rc = resolve_decisions(c)) return rc;
+    if (int rc = check_deferred(c)) return rc;
+    scores_invalidate(c);   // the run rewrites the column the tape reads
+    c->wseq += 1;           // ... and the weights
+    int32_t cx = -1;
+    if (int rc = wsmc_col_create(c, "x", 1, &cx)) return rc;
+    if (c->lg_data_cap < T) {
+        WSMC_HIP(ctx_sync(c, c->stream));
+        if (c->lg_data) WSMC_HIP(hipFree(c->lg_data));
+        c->lg_data = nullptr;
+        c->lg_data_cap = 0;
+        WSMC_HIP(hipMalloc(&c->lg_data, sizeof(double) * (size_t)T));
+        c->lg_data_cap = T;
+    }
+    if (ess_trace_out && c->lg_trace_cap < T) {
+        WSMC_HIP(ctx_sync(c, c->stream));
+        if (c->lg_trace) WSMC_HIP(hipFree(c->lg_trace));
+        c->lg_trace = nullptr;
+        c->lg_trace_cap = 0;
+        WSMC_HIP(hipMalloc(&c->lg_trace, sizeof(double) * (size_t)T));
+        c->lg_trace_cap = T;
+    }
+    if (!c->lg_rec) WSMC_HIP(hipMalloc(&c->lg_rec, sizeof(LgRecord)));
+    WSMC_HIP(hipMemcpyAsync(c->lg_data, data, sizeof(double) * (size_t)T, hipMemcpyHostToDevice, c->stream));
+    WSMC_HIP(hipMemsetAsync(c->lg_rec, 0, sizeof(LgRecord), c->stream));
+    LgArgs ka;
+    std::memset(&ka, 0, sizeof(ka));
+    ka.x = c->cols[cx].front;
+    ka.w = c->w;
+    ka.anc = c->anc;
+    ka.data = c->lg_data;
+    ka.ess_trace = ess_trace_out ? c->lg_trace : nullptr;
+    ka.rec = c->lg_rec;
+    ka.N = (int32_t)c->N;
+    // two particles a thread where the workgroup allows: each wave's reductions, scans and barriers
+    // cost a step more than a second particle in its lanes does (N = 1000 measured
+    // at 64 .. 1024 threads, 512 the fastest)
+    const int threads = std::max(64, std::min<int>(kLgThreads, (int)((c->N + 127) / 128) * 64));
+    ka.P = (int32_t)((c->N + threads - 1) / threads);
+    ka.scheme = scheme;
+    ka.seed = c->seed;
+    ka.op_base = c->op;
+    ka.a = a;
+    ka.q = q;
+    ka.x0_std = x0_std;
+    ka.c = wsmc_normal_c(wsmc_log(r));      // the Observe's per-sigma pair (wsmc_normal_scale)
+    ka.rh = wsmc_normal_rh(1.0 / r);
+    ka.ess_min = ess_min;
+    // every segment back to back on the stream; the state between them is x's column, w, anc and rec
+    const int32_t K = c->lg_segment > 0 ? c->lg_segment : kLgSegmentSteps;
+    int64_t nseg = 0;
+    for (int32_t t0 = 0; t0 < T; t0 += K, ++nseg) {
+        ka.t0 = t0;
+        ka.nsteps = std::min<int32_t>(K, T - t0);
+        ka.first = t0 == 0;
+        WSMC_HIP(launch_lgssm_segment(c->stream, ka, threads));
+    }
+    LgRecord hrec;
+    WSMC_HIP(hipMemcpyAsync(&hrec, c->lg_rec, sizeof(LgRecord), hipMemcpyDeviceToHost, c->stream));
+    if (ess_trace_out)
+        WSMC_HIP(hipMemcpyAsync(ess_trace_out, c->lg_trace, sizeof(double) * (size_t)T, hipMemcpyDeviceToHost,
+                                c->stream));
+    // the bookkeeping of the statements issued one by one, while the device runs
+    const auto t_book = clk::now();
+    wrote_col(c, cx);
+    gc_log(c);
+    c->tape.reserve(c->tape.size() + 1 + 2 * (size_t)T);
+    push_sample_term(c, cx, lg_normal(-1, 0.0, x0_std));
+    c->depth += 1;
+    {
+        const wsmc_dist trans = lg_normal(cx, a, q);
+        wsmc_term ob;
+        std::memset(&ob, 0, sizeof(ob));
+        ob.dist = lg_normal(cx, 1.0, r);
+        ob.kind = WSMC_TERM_OBSERVE;
+        for (int32_t t = 0; t < T; ++t) {
+            push_sample_term(c, cx, trans);
+            c->depth += 1;
+            lg_const4(data[t], ob.x);
+            ob.depth = c->depth;
+            c->tape.push_back(ob);
+            c->depth += 1;
+        }
+    }
+    c->op += 2 + 3 * (uint64_t)T;
+    c->weights_changed = 0;
+    const auto t_booked = clk::now();
+    WSMC_HIP(ctx_sync(c, c->stream));
+    c->resampled = hrec.last_dec;
+    c->last_ess = hrec.last_ess;
+    c->n_resamples += hrec.nres;
+    if (hrec.nres) set_anc_last(c, nullptr, -1);   // the last resampling step's row is in c->anc
+    c->wseq += 1;
+    c->lg_runs += 1;
+    c->lg_segments += nseg;
+    c->lg_book_us = us(t_book, t_booked);
+    if (log_evidence_out)
+        if (int rc = wsmc_log_evidence(c, log_evidence_out)) return rc;
+    c->lg_wall_us = us(t_in, clk::now());
+    return WSMC_OK;
+}
+
+int wsmc_debug_lgssm(wsmc_ctx* c, int32_t segment_steps, int64_t* stats_out) {
+    if (!c) return fail(WSMC_EARG, "null context");
+    wsmc_ctx* sc = c->multi ? multi_first(c) : c;
+    if (segment_steps >= 0) sc->lg_segment = segment_steps;
+    if (stats_out) {
+        stats_out[0] = kLgCap;
+        stats_out[1] = sc->lg_runs;
+        stats_out[2] = sc->lg_stmt_runs;
+        stats_out[3] = sc->lg_segments;
+        stats_out[4] = sc->lg_book_us;
+        stats_out[5] = sc->lg_wall_us;
+    }
     return WSMC_OK;
 }
 

@@ -126,6 +126,7 @@ struct RunGraph {
 
 struct MultiState;   // wsmc_multi.hip
 struct EwBatch;      // below
+struct LgRecord;     // below
 }  // namespace wsmc
 
 struct wsmc_ctx {
@@ -367,6 +368,14 @@ struct wsmc_ctx {
     double* xscratch = nullptr;             // [2N]
     uint64_t* run_params = nullptr;         // [8] device copy of per-run values (op base)
     std::vector<wsmc::RunGraph> graphs;
+    // fused 1D LGSSM run (wsmc_lgssm1d_run)
+    double* lg_data = nullptr;              // [lg_cap_T] the run's observations
+    double* lg_trace = nullptr;             // [lg_cap_T] its ESS trace (allocated when first requested)
+    int64_t lg_data_cap = 0, lg_trace_cap = 0;
+    wsmc::LgRecord* lg_rec = nullptr;       // [1]
+    int32_t lg_segment = 0;                 // steps per launch (0: kLgSegmentSteps)
+    int64_t lg_runs = 0, lg_stmt_runs = 0, lg_segments = 0;   // cumulative (wsmc_debug_lgssm)
+    int64_t lg_book_us = 0, lg_wall_us = 0; // the last run's host bookkeeping / whole call, microseconds
     bool timing = false;
     std::vector<hipEvent_t> events;
     wsmc_run_timing last_timing{};
@@ -849,6 +858,35 @@ hipError_t launch_run_head(hipStream_t s, const RunHead& h);
 hipError_t launch_ssm2d_finalize(hipStream_t s, const Ssm2dFinal& f, hipEvent_t e0 = nullptr,
                                  hipEvent_t e1 = nullptr);
 hipError_t launch_delay(hipStream_t s, int microseconds);
+// fused 1D LGSSM (csrc/wsmc_lgssm.hip): one persistent workgroup, the population in LDS. Per
+// particle the kernel holds x, a second x / CDF buffer, the log-weight (8 B each) and an ancestor
+// (4 B): 28 B, so 5120 particles take 140 KiB of the workgroup's 160 KiB (+ 4 KiB of log / exp
+// tables, 1 KiB of reduction scratch: 145 KiB in all)
+constexpr int kLgCap = 5120;            // the largest N the persistent kernel takes
+constexpr int kLgThreads = 1024;
+constexpr int kLgSegmentSteps = 2048;   // steps per launch by default (wsmc_debug_lgssm)
+struct LgRecord {             // the run's state between segments, beside x's column, w and anc
+    long long nres;           // steps that resampled so far
+    int32_t last_dec, pad;    // the last step's decision
+    double last_ess;          // ... and ESS%
+};
+struct LgArgs {
+    double* x;                // [N] the column (read unless `first`, written at the segment's end)
+    double* w;                // [N] log-weights
+    int32_t* anc;             // [N] written when a step of the segment resampled
+    const double* data;       // [T] observations
+    double* ess_trace;        // [T] or null
+    LgRecord* rec;
+    int32_t N, P;             // particles, particles per thread
+    int32_t t0, nsteps;       // the segment's steps [t0, t0 + nsteps)
+    int32_t first, scheme;    // first: the segment starts the run (x ~ Normal(0, x0_std))
+    uint64_t seed, op_base;   // op_base: the op counter at the run's start
+    double a, q, x0_std;
+    double c, rh;             // the Observe's wsmc_normal_c(log r), wsmc_normal_rh(1 / r)
+    double ess_min;
+};
+size_t lgssm_lds_bytes(int n);
+hipError_t launch_lgssm_segment(hipStream_t s, const LgArgs& a, int threads);
 // one handle over several devices (wsmc_multi.hip): the ABI entry points fan out
 int multi_destroy(wsmc_ctx* c);
 wsmc_ctx* multi_first(wsmc_ctx* c);

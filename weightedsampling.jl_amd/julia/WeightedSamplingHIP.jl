@@ -726,4 +726,28 @@ function ssm2d_run!(state::HipState, obs::AbstractMatrix; x0=(0.0, 0.0), v0=(1.0
     return ev[]
 end
 
+"""
+    lgssm1d_run!(state, data; a=0.9, q=1.0, r=0.5, x0_std=1.0, ess_trace=false) -> log_evidence[, trace]
+
+benchmarks/ssm/WeightedSampling/lgssm1d.jl:18-24 as one call (`wsmc_lgssm1d_run`): column `x`,
+weights, flags and RNG positions as `run!` of the model leaves them. A population within the
+persistent kernel's cap runs on one workgroup with no launch per step; larger ones, sharded
+states and multinomial resampling issue the statements inside the library. With `ess_trace` the
+ESS% of every step's post-Observe Resample comes back too. (Written against the C ABI; not run
+in this repository's checks, which have no Julia.)
+"""
+function lgssm1d_run!(state::HipState, data::AbstractVector; a=0.9, q=1.0, r=0.5, x0_std=1.0,
+                      scheme=RESAMPLE_STRATIFIED, ess_trace=false)
+    d = Vector{Float64}(data)
+    ev = Ref{Float64}(0.0)
+    tr = ess_trace ? Vector{Float64}(undef, length(d)) : Float64[]
+    check(ccall((:wsmc_lgssm1d_run, libwsmc), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Int32, Float64, Float64, Float64, Float64, Float64, Int32,
+                 Ptr{Float64}, Ptr{Float64}),
+                state.store.ctx, d, length(d), a, q, r, x0_std, state.ess_perc_min, scheme, ev,
+                ess_trace ? tr : C_NULL))
+    mirror_flags!(state)
+    return ess_trace ? (ev[], tr) : ev[]
+end
+
 end # module

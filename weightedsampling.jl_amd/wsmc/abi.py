@@ -156,6 +156,9 @@ SIGNATURES = {
     "wsmc_last_ancestors": (C.c_int, [_P, _I32P]),
     "wsmc_ssm2d_run": (C.c_int, [_P, _D, C.c_int32, _D, _D, C.c_double, C.c_double, C.c_double,
                                  C.c_int32, C.c_int32, _D]),
+    "wsmc_lgssm1d_run": (C.c_int, [_P, _D, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                   C.c_int32, _D, _D]),
+    "wsmc_debug_lgssm": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int64)]),
     "wsmc_run_set_timing": (C.c_int, [_P, C.c_int32]),
     "wsmc_run_get_timing": (C.c_int, [_P, C.POINTER(RunTiming)]),
     "wsmc_debug_kernel_bench": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _D]),

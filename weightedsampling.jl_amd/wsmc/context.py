@@ -418,6 +418,36 @@ class Context:
                                      C.byref(ev) if want_evidence else None))
         return float(ev.value) if want_evidence else None
 
+    def lgssm1d_run(self, data, a=0.9, q=1.0, r=0.5, x0_std=1.0, ess_perc_min=1.0,
+                    scheme: int = abi.RESAMPLE_STRATIFIED, want_evidence: bool = True, ess_trace: bool = False):
+        """The 1D linear-Gaussian SSM of models.lgssm1d_statements as one call (wsmc_lgssm1d_run):
+        the same column, weights, ancestors, state and RNG positions. Returns the log evidence
+        (None without want_evidence), or (evidence, trace) with ess_trace: the ESS% of every
+        step's post-Observe Resample."""
+        d = np.ascontiguousarray(np.asarray(data, dtype=np.float64).reshape(-1))
+        ev = C.c_double()
+        tr = np.empty(len(d)) if ess_trace else None
+        check(self._L.wsmc_lgssm1d_run(self._h, _dptr(d), len(d), float(a), float(q), float(r), float(x0_std),
+                                       float(ess_perc_min), int(scheme), C.byref(ev) if want_evidence else None,
+                                       _dptr(tr) if ess_trace else None))
+        e = float(ev.value) if want_evidence else None
+        return (e, tr) if ess_trace else e
+
+    def lgssm_stats(self) -> dict:
+        """wsmc_debug_lgssm's counters: the persistent kernel's particle cap, the runs it took, the
+        runs that went through the statement route, the segments launched (cumulative), and the
+        last run's host bookkeeping and whole-call seconds."""
+        st = (C.c_int64 * 6)()
+        check(self._L.wsmc_debug_lgssm(self._h, -1, st))
+        return {"cap": st[0], "persistent_runs": st[1], "statement_runs": st[2], "segments": st[3],
+                "bookkeeping_s": st[4] / 1e6, "call_s": st[5] / 1e6}
+
+    def set_lgssm_segment(self, steps: int) -> None:
+        """Steps per launch of the persistent LGSSM kernel (0 restores the default)."""
+        if steps < 0:
+            raise ValueError("steps must be >= 0")
+        check(self._L.wsmc_debug_lgssm(self._h, int(steps), None))
+
     def set_timing(self, enabled: bool) -> None:
         check(self._L.wsmc_run_set_timing(self._h, int(bool(enabled))))
 
