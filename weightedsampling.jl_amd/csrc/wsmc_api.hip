@@ -848,6 +848,7 @@ int wsmc_nparticles(wsmc_ctx* c, int64_t* n) {
 int wsmc_get_state(wsmc_ctx* c, wsmc_state* s) {
     if (c && c->multi) return s ? multi_get_state(c, s) : fail(WSMC_EARG, "null argument");
     if (!c || !s) return fail(WSMC_EARG, "null argument");
+    CHECK_CTX_EW(c);   // an asynchronous fused run's decisions are part of the state: fold it in first
     if (int r = resolve_decisions(c)) return r;
     if (int r = check_deferred(c)) return r;
     s->resampled = c->resampled;
@@ -3809,6 +3810,17 @@ static int run_qstat_mode(int64_t N) {
 #endif
 }
 
+// The propagate that takes the statistics is resident in one round of blocks up to 1M particles at
+// 4 blocks a CU (8 waves a SIMD); a population of many rounds streams faster at 3 (measured
+// alternated, DESIGN.md §3: 8M 19.64-19.82 ms a run at 3 against 19.92-20.20 at 4). The switch is
+// where the statistics mode switches. WSMC_PROP_BLOCKS = 3 / 4 forces either (tests; no result
+// depends on it), read at every run.
+static bool prop_three_blocks(int64_t N) {
+    const char* e = getenv("WSMC_PROP_BLOCKS");
+    if (e && (atoi(e) == 3 || atoi(e) == 4)) return atoi(e) == 3;
+    return N >= kQstatRecomputeN;
+}
+
 // events (timing mode): per step 8 = {prop, sums, reduce, scan} x {start, stop} bound to the
 // dispatches themselves (hipExtLaunchKernelGGL), then 2 for the finalize kernel
 // a parity's pinned staging: [op-base bits, pad, obs 2T] (ensure_run_buffers sizes it)
@@ -3856,6 +3868,7 @@ static int enqueue_ssm2d(wsmc_ctx* c, const RunPlan& p, const std::vector<hipEve
     // with a miss on the exact path (wsmc_ssm2d_run); sharded: k_rs_qfix checks and recomputes in
     // place (the shards' decisions are global, so a replay would have to be too).
     const int qs = p.scheme == WSMC_RESAMPLE_MULTINOMIAL || p.exact_stats ? 0 : run_qstat_mode(N);
+    const bool three_blocks = prop_three_blocks(N);
     for (int t = 1; t <= T; ++t) {
         const bool guess = qs && t > 1;
         Ssm2dArgs a;
@@ -3901,6 +3914,7 @@ static int enqueue_ssm2d(wsmc_ctx* c, const RunPlan& p, const std::vector<hipEve
             a.w_save = c->run_w0 + (size_t)par * N;
         if (guess) {   // stratified / systematic: the propagate takes the Resample statistics too
             a.qstat = true;
+            a.three_blocks = three_blocks;
             a.ms_prev = t > 1 ? c->run_max + (t - 1) : nullptr;
             a.rg_out = c->run_rg + t;
             a.tilep = c->tilep;

@@ -29,7 +29,9 @@ namespace wsmc {
 // WSMC_DIAG_CAPTURE_FAIL (the eager fallback after a failed graph capture), WSMC_DIAG_NO_PEER
 // (exact shards trace lineages through windows instead of peer reads), WSMC_EXACT_EAGER (the
 // host-driven exact-shard run), WSMC_EAGER_GATHER (columns gathered at each Resample instead of
-// lazily), and WSMC_JIT_DUMP / WSMC_JIT_VERBOSE / WSMC_TRACE_DEBUG (diagnostic output only).
+// lazily), WSMC_PROP_BLOCKS (3 / 4: the blocks a CU admits of the fused run's propagate, chosen
+// by the population's size otherwise), and WSMC_JIT_DUMP / WSMC_JIT_VERBOSE / WSMC_TRACE_DEBUG
+// (diagnostic output only).
 inline const char* diag_env(const char* name) {
 #ifdef WSMC_DIAG_BUILD
     return getenv(name);
@@ -802,6 +804,9 @@ struct Ssm2dArgs {
     // k_rs_qfix), this step's tile partials and group lines, and q itself when the fill reads it
     // (null: the fill recomputes q from the weights)
     bool qstat = false;
+    // (launch only) 3 blocks a CU instead of the 4 the QS propagate's registers allow: beyond one
+    // round of blocks the lower occupancy is the faster one
+    bool three_blocks = false;
     double* w_save = nullptr;          // the first step's incoming weights go here (a replay's start)
     const MaxSlots* ms_prev = nullptr;
     double* rg_out = nullptr;

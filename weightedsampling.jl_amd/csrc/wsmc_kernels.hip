@@ -20,6 +20,30 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 
 typedef unsigned long long u64;
 
+// Block clocks (diagnostic build only; tools/block_rounds.py): thread 0 of every block of the
+// propagate (0; 3 without the Resample statistics), the fill (1) and the trace-back (2) stores the constant 100 MHz clock at its
+// start and at its end, one plain vector store each, so the tool can count how many blocks were
+// alive at once and how many started only after the first one had retired (the rounds of
+// DESIGN.md §3). A launch overwrites the launch before it. The product build carries none of it.
+#ifdef WSMC_DIAG_BUILD
+constexpr int kClkKinds = 4, kClkBlocks = 16384;
+__device__ u64 g_blk_clk[kClkKinds][kClkBlocks][2];
+struct BlkClock {
+    int kind;
+    u64 t0;
+    __device__ __forceinline__ explicit BlkClock(int k) : kind(k), t0(wall_clock64()) {}
+    __device__ __forceinline__ ~BlkClock() {
+        if (threadIdx.x == 0 && blockIdx.x < (unsigned)kClkBlocks) {
+            g_blk_clk[kind][blockIdx.x][0] = t0;
+            g_blk_clk[kind][blockIdx.x][1] = wall_clock64();
+        }
+    }
+};
+#define WSMC_BLK_CLOCK(kind) const BlkClock blk_clock_(kind)
+#else
+#define WSMC_BLK_CLOCK(kind)
+#endif
+
 // ------------------------------------------------------------------------------------
 // wave / block primitives (wave64)
 // Cross-lane moves are DPP (a VALU operand modifier) rather than ds_bpermute (an LDS
@@ -1811,6 +1835,7 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(WSMC
                                                               ShardRecord* rec, Decision* dec,
                                                               const u64* __restrict__ qbuf, int32_t* __restrict__ anc,
                                                               const double* __restrict__ wq) {
+    WSMC_BLK_CLOCK(1);
     __shared__ FillLds sh;
     __shared__ u64 s_red[kScanBlock / 64][2];
     __shared__ u64 s_parts[kScanBlock / 64][kRedPart];
@@ -3235,60 +3260,88 @@ __device__ __forceinline__ double aff2(double a, double b) {
 // -c0/2: every weight of the step is <= U (rounding is monotone), so R_g >= ceil(M), and R_g is
 // the canonical ceil(M) unless M and U straddle an integer. k_rs_qfix checks that once M is
 // known and recomputes the statistics when it is not (include/wsmc_math.h wsmc_qref).
-template <int MODE, int IT = 1, int NT = kBlock, bool QS = false>
+// ISL (QS only): an island shard, which takes the previous step's decision here from its
+// all-gathered records; the one-GPU instantiation carries none of that path. A QS launch is never
+// the first step (it has no bound to guess from) nor an exact shard, so those operands (x0, v0,
+// w_save, identity, xr, vr) are compiled out of it: with the decision path they are what held the
+// kernel above 80 scalar registers, and from 98 a SIMD admits 6 waves, 3 blocks of 512 a CU, so
+// 768 of a 1M run's 977 blocks in the first round (tests/test_kernel_residency.py
+// holds the one-GPU instantiation to 80). The island instantiation still takes 106.
+// The loads at the head of the block's dependent chain (the ancestor pair, the previous decision,
+// the previous max slots) are issued before the log table is staged, so the table's round trip
+// and its barrier overlap them instead of preceding them.
+template <int MODE, int IT = 1, int NT = kBlock, bool QS = false, bool ISL = false>
 __global__ __launch_bounds__(NT) void k_ssm2d_prop(Ssm2dArgs a) {
+    WSMC_BLK_CLOCK(QS ? 0 : 3);
+    static_assert(QS || !ISL, "ISL selects the decision path of the QS instantiations");
     __shared__ u64 lds4[NT / 64];
     __shared__ double s_logtab[2 * WSMC_LOG_TABLE_N];
-    if (WSMC_PROP_LDS_LOG && (MODE & 1) == 0) {   // every thread, before the first draw
-        const double* lt = wsmc_log_table();
-        for (int k = (int)threadIdx.x; k < 2 * WSMC_LOG_TABLE_N; k += NT) s_logtab[k] = lt[k];
-        __syncthreads();
-    }
-    const double* logtab = WSMC_PROP_LDS_LOG ? s_logtab : wsmc_log_table();
+    __shared__ Decision s_dec;
     const int64_t N = a.N;
-    bool rs;
-    double mean;
-    if (a.recs_prev && a.t > 1) {
-        __shared__ Decision s_dec;
-        if (threadIdx.x == 0) {
-            Decision dd;
-            decide_records(a.recs_prev, a.world, a.rank, a.ess_min, &dd);
-            s_dec = dd;
-            if (blockIdx.x == 0) *a.dec_out = dd;
-        }
-        __syncthreads();
-        rs = s_dec.resampled;
-        mean = rs ? s_dec.mean : 0.0;
-    } else {
-        rs = a.t > 1 && a.dec_prev->resampled;
-        mean = rs ? a.dec_prev->mean : 0.0;
-    }
-    const uint64_t op_dv = a.op_dev[0] + 3ull * (uint64_t)(a.t - 1);
-    const double o0 = a.obs[2 * (a.t - 1)], o1 = a.obs[2 * (a.t - 1) + 1];
+    const bool first = !QS && a.t == 1;
+    const bool isl = QS ? ISL : (a.recs_prev != nullptr && a.t > 1);
+    const bool identity = !QS && a.identity;
     // IT pairs per thread, a grid apart: every pair's loads are issued before any pair is
     // computed and stored, so one pair's stores overlap the next pair's reads
     const int64_t stride = (int64_t)gridDim.x * NT * 2;
     const int64_t ib = ((int64_t)blockIdx.x * NT + threadIdx.x) * 2;
-    int64_t src[IT][2];
+    // the ancestors are loaded speculatively (the previous step's row always exists at t > 1):
+    // first of all, ahead of the decision they are selected by and of the table's barrier
+    int2 s2[IT];
     bool ok[IT], two[IT];
 #pragma unroll
     for (int j = 0; j < IT; ++j) {
         const int64_t i0 = ib + (int64_t)j * stride;
         ok[j] = i0 < N;
         two[j] = i0 + 1 < N;
-        src[j][0] = i0; src[j][1] = i0 + 1;
-        // the ancestors are loaded speculatively (the previous step's row always exists at
-        // t > 1), in parallel with the decision flag, not after it
-        if (ok[j] && a.t > 1 && (MODE & 2) == 0 && !a.identity) {
-            int2 s2;
+        s2[j] = int2{0, 0};
+        if (QS && (MODE & 2) == 0) {
+            // one load under no branch (the join of a branch waits for the load): the fused run's
+            // ancestor rows are padded to 4 entries, so the pair at an even i0 < N lies inside the
+            // row (its second entry is not used when i0 + 1 == N); threads past N read pair 0
+            s2[j] = *reinterpret_cast<const int2*>(a.anc_prev + (ok[j] ? i0 : 0));
+        } else if (ok[j] && !first && (MODE & 2) == 0 && !identity) {
             if (two[j]) {
-                s2 = *reinterpret_cast<const int2*>(a.anc_prev + i0);
+                s2[j] = *reinterpret_cast<const int2*>(a.anc_prev + i0);
             } else {
-                s2.x = a.anc_prev[i0];
-                s2.y = 0;
+                s2[j].x = a.anc_prev[i0];
             }
-            if (rs) { src[j][0] = s2.x; src[j][1] = s2.y; }
         }
+    }
+    u64 mprev = 0;     // QS: the previous step's max slots (the bound when it did not resample)
+    if (QS) mprev = a.ms_prev->v[threadIdx.x & 63][0];
+    if (isl) {
+        if (threadIdx.x == 0) {
+            Decision dd;
+            decide_records(a.recs_prev, a.world, a.rank, a.ess_min, &dd);
+            s_dec = dd;
+            if (blockIdx.x == 0) *a.dec_out = dd;
+        }
+    }
+    const uint64_t op_dv = a.op_dev[0] + 3ull * (uint64_t)(a.t - 1);
+    const double o0 = a.obs[2 * (a.t - 1)], o1 = a.obs[2 * (a.t - 1) + 1];
+    bool rs = false;
+    double mean = 0.0;
+    if (!isl && !first) {
+        rs = a.dec_prev->resampled;
+        mean = rs ? a.dec_prev->mean : 0.0;
+    }
+    if (WSMC_PROP_LDS_LOG && (MODE & 1) == 0) {   // every thread, before the first draw
+        const double* lt = wsmc_log_table();
+        for (int k = (int)threadIdx.x; k < 2 * WSMC_LOG_TABLE_N; k += NT) s_logtab[k] = lt[k];
+    }
+    if ((WSMC_PROP_LDS_LOG && (MODE & 1) == 0) || isl) __syncthreads();   // the table and the island decision
+    const double* logtab = WSMC_PROP_LDS_LOG ? s_logtab : wsmc_log_table();
+    if (isl) {
+        rs = s_dec.resampled;
+        mean = rs ? s_dec.mean : 0.0;
+    }
+    int64_t src[IT][2];
+#pragma unroll
+    for (int j = 0; j < IT; ++j) {
+        const int64_t i0 = ib + (int64_t)j * stride;
+        src[j][0] = i0; src[j][1] = i0 + 1;
+        if (ok[j] && !first && (MODE & 2) == 0 && !identity && rs) { src[j][0] = s2[j].x; src[j][1] = s2[j].y; }
     }
     d2 xp[IT][2], vp[IT][2];
     double wb[IT][2];
@@ -3301,15 +3354,15 @@ __global__ __launch_bounds__(NT) void k_ssm2d_prop(Ssm2dArgs a) {
             if (two[j]) {
                 const d2 w2 = *reinterpret_cast<const d2*>(a.w + i0);
                 wb[j][0] = w2.x; wb[j][1] = w2.y;
-                if (a.w_save) *reinterpret_cast<d2*>(a.w_save + i0) = w2;
+                if (!QS && a.w_save) *reinterpret_cast<d2*>(a.w_save + i0) = w2;
             } else {
                 wb[j][0] = a.w[i0];
-                if (a.w_save) a.w_save[i0] = wb[j][0];
+                if (!QS && a.w_save) a.w_save[i0] = wb[j][0];
             }
         }
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-            if (a.t == 1) {
+            if (first) {
                 xp[j][k] = d2{a.x0[0], a.x0[1]};
                 vp[j][k] = d2{a.v0[0], a.v0[1]};
             } else if (k == 0 || two[j]) {
@@ -3332,8 +3385,7 @@ __global__ __launch_bounds__(NT) void k_ssm2d_prop(Ssm2dArgs a) {
     double Rg = 0.0, sK = 0.0;
     if (QS) {
         // the guess: every weight of this step is wb + lp <= base + lpmax (lp <= -c0/2, wb <= base)
-        double base = WSMC_NAN;   // the first step: no bound (k_rs_qfix takes the statistics)
-        if (a.t > 1 && a.ms_prev) base = rs ? mean : wave_slots_max(a.ms_prev);
+        const double base = rs ? mean : wsmc_ord_dec(wave_max_u64(mprev));
         const double lpmax = -(a.c0 + 0.0) * 0.5;
         Rg = wsmc_qref(base + lpmax);
         sK = wsmc_pow2i(wsmc_qbits((uint64_t)N));
@@ -3504,6 +3556,7 @@ typedef double __attribute__((address_space(1)))* gdp;
 // stores, 2 = the ancestor chain alone
 template <bool ISL, int P, int DG = 0>
 __global__ __launch_bounds__(kBlock) void k_ssm2d_final(Ssm2dFinal f) {
+    WSMC_BLK_CLOCK(2);
     const int64_t N = f.N;
     const int64_t i0 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * P;
     const int T = f.T;
@@ -3837,6 +3890,16 @@ static hipError_t launch_timed(K kernel, dim3 grid, dim3 block, hipStream_t s, h
         hipExtLaunchKernelGGL(kernel, grid, block, 0, s, e0, e1, 0, args...);
     else
         hipLaunchKernelGGL(kernel, grid, block, 0, s, args...);
+    return hipGetLastError();
+}
+// the same with dynamic LDS the kernel does not use: it only bounds the blocks a CU admits
+template <typename K, typename... Args>
+static hipError_t launch_timed_lds(K kernel, dim3 grid, dim3 block, unsigned lds, hipStream_t s, hipEvent_t e0,
+                                   hipEvent_t e1, Args... args) {
+    if (e0 || e1)
+        hipExtLaunchKernelGGL(kernel, grid, block, lds, s, e0, e1, 0, args...);
+    else
+        hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
     return hipGetLastError();
 }
 
@@ -4495,7 +4558,13 @@ static int prop_mode() {
 #endif
 hipError_t launch_ssm2d_propagate(hipStream_t s, const Ssm2dArgs& a, hipEvent_t e0, hipEvent_t e1) {
     if (a.qstat)   // one 1024-particle Resample tile a block
-        return launch_timed(k_ssm2d_prop<0, 1, 512, true>, rs_tiles_for(a.N), dim3(512), s, e0, e1, a);
+    {
+        // a.three_blocks: 44 KB of unused dynamic LDS a block, so that a CU's 160 KB admit 3 blocks
+        // and not the 4 its registers allow (many rounds anyway: 6 waves a SIMD stream faster)
+        const unsigned lds = a.three_blocks ? 44u * 1024u : 0u;
+        return a.recs_prev ? launch_timed_lds(k_ssm2d_prop<0, 1, 512, true, true>, rs_tiles_for(a.N), dim3(512), lds, s, e0, e1, a)
+                           : launch_timed_lds(k_ssm2d_prop<0, 1, 512, true>, rs_tiles_for(a.N), dim3(512), lds, s, e0, e1, a);
+    }
     const dim3 g((unsigned)((a.N + 2 * kBlock - 1) / (2 * kBlock)));
     // IT = 2 / 4 pairs per thread (grid / 2, / 4) measured 18.8 / 22.2 us against 17.0 (1M)
     if (a.xr) return launch_timed(k_ssm2d_prop<16>, g, dim3(kBlock), s, e0, e1, a);   // exact shards
@@ -4558,3 +4627,20 @@ hipError_t launch_ssm2d_finalize(hipStream_t s, const Ssm2dFinal& f, hipEvent_t 
 }
 
 }  // namespace wsmc
+
+#ifdef WSMC_DIAG_BUILD
+// the block clocks of the last propagate / fill / trace-back launch (kind 0 / 1 / 2): out gets
+// nblocks {start, end} pairs; nblocks < 0 zeroes every kind (tools/block_rounds.py)
+extern "C" int wsmc_diag_block_clocks(int kind, unsigned long long* out, int nblocks) {
+    using namespace wsmc;
+    if (nblocks < 0) {
+        void* p = nullptr;
+        if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_blk_clk)) != hipSuccess) return -1;
+        return hipMemset(p, 0, sizeof(g_blk_clk)) == hipSuccess ? 0 : -1;
+    }
+    if (kind < 0 || kind >= kClkKinds || nblocks > kClkBlocks) return -1;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_blk_clk), sizeof(u64) * 2 * (size_t)nblocks,
+                               sizeof(u64) * 2 * (size_t)kClkBlocks * (size_t)kind, hipMemcpyDeviceToHost) == hipSuccess
+               ? 0 : -1;
+}
+#endif
