@@ -82,7 +82,19 @@ typedef enum {
     WSMC_FAM_LOGISTIC = 11,     /* Logistic(mu, theta)                              */
     WSMC_FAM_GUMBEL = 12,       /* Gumbel(mu, theta)                                */
     WSMC_FAM_RAYLEIGH = 13,     /* Rayleigh(sigma = scale)                          */
-    WSMC_FAM_GEOMETRIC = 14     /* Geometric(p = mu[0]): failures before the first success */
+    WSMC_FAM_GEOMETRIC = 14,    /* Geometric(p = mu[0]): failures before the first success */
+    /* 15 is reserved: it stays an unknown family (WSMC_EARG). */
+    /* the families of src/default_kernels.jl:83-102 built on log Gamma (wsmc_lgamma) and
+       bounded rejection samplers (wsmc_terms.h); first parameter mu[0], second `scale`: */
+    WSMC_FAM_GAMMA = 16,        /* Gamma(alpha = mu[0], theta = scale), theta a scale        */
+    WSMC_FAM_INVERSEGAMMA = 17, /* InverseGamma(alpha = mu[0], theta = scale), theta a scale */
+    WSMC_FAM_CHISQ = 18,        /* Chisq(nu = mu[0])                                        */
+    WSMC_FAM_BETA = 19,         /* Beta(alpha = mu[0], beta = scale)                        */
+    WSMC_FAM_TDIST = 20,        /* TDist(nu = mu[0])                                        */
+    WSMC_FAM_POISSON = 21,      /* Poisson(lambda = mu[0])                                  */
+    WSMC_FAM_BINOMIAL = 22,     /* Binomial(n = mu[0], p = scale)                           */
+    WSMC_FAM_NEGBINOMIAL = 23   /* NegativeBinomial(r = mu[0] > 0 real, p = scale): failures
+                                   before the r-th success                                  */
 } wsmc_family;
 
 typedef enum {
@@ -456,7 +468,9 @@ int wsmc_debug_exact(wsmc_ctx* ctx, int64_t cap, int64_t ctr, int64_t* stats_out
  * the interpreter kernel), batches launched on compiled kernels, batches run on the
  * interpreter, total compile time (us) — process-wide. */
 int wsmc_debug_jit_stats(int64_t* stats_out);
-/* Compile a representative batch signature (the 2D SSM step) for gfx950 without a device:
+/* Compile representative batch signatures (the 2D SSM step, with and without the Resample
+ * statistics, and four log-Gamma batches with column parameters: NegativeBinomial and Binomial each
+ * drawn and scored, six Samples a batch, the other families) for gfx950 without a device:
  * WSMC_OK, or WSMC_EHIP with hiprtc's log in wsmc_last_error(). */
 int wsmc_debug_jit_selfcheck(void);
 /* The Move acceptance screen (csrc/wsmc_kernels.hip move_accept) on the current device: for each

@@ -141,11 +141,15 @@ WSMC_HD double wsmc_xeval(const wsmc_xinst* p, int n, double* const* cols, int64
 /* feat: the mean functions and families a caller may meet (WSMC_FEAT_OSC: the oscillator,
  * WSMC_FEAT_MVN: the full-covariance MvNormal). A device kernel launched without them passes
  * 0 (or OSC alone), so their code is not compiled into it (registers); every other caller
- * passes WSMC_FEAT_ALL. The arithmetic is the same. */
+ * passes WSMC_FEAT_ALL. The arithmetic is the same. WSMC_FEAT_BASE is the set without the
+ * log-Gamma families: the device launchers keep an instantiation on it, so a Bernoulli or
+ * MvNormal statement does not carry wsmc_lgamma and the rejection samplers. */
 #define WSMC_FEAT_OSC 1u
 #define WSMC_FEAT_MVN 2u   /* the full-covariance MvNormal family */
-#define WSMC_FEAT_EXT 4u   /* the scalar families from WSMC_FAM_BERNOULLI on */
-#define WSMC_FEAT_ALL 7u
+#define WSMC_FEAT_EXT 4u   /* the scalar families WSMC_FAM_BERNOULLI .. WSMC_FAM_GEOMETRIC */
+#define WSMC_FEAT_GAM 8u   /* the log-Gamma families WSMC_FAM_GAMMA .. WSMC_FAM_NEGBINOMIAL */
+#define WSMC_FEAT_BASE 7u
+#define WSMC_FEAT_ALL 15u
 WSMC_HD double wsmc_dist_mean_f(const wsmc_dist* d, int k, double* const* cols, int64_t N, int64_t i,
                                 const wsmc_override* ov, unsigned feat) {
     if ((feat & WSMC_FEAT_OSC) && d->mean_fn == WSMC_MEAN_OSCILLATOR) {
@@ -305,7 +309,8 @@ WSMC_HD void wsmc_mvn_sample_n(const wsmc_dist* d, const int n, double* x, uint6
 WSMC_HD unsigned wsmc_dist_feat(const wsmc_dist* d) {
     return (d->mean_fn == WSMC_MEAN_OSCILLATOR ? WSMC_FEAT_OSC : 0u) |
            (d->family == WSMC_FAM_MVNORMAL ? WSMC_FEAT_MVN : 0u) |
-           (d->family >= WSMC_FAM_BERNOULLI ? WSMC_FEAT_EXT : 0u);
+           (d->family >= WSMC_FAM_BERNOULLI && d->family <= WSMC_FAM_GEOMETRIC ? WSMC_FEAT_EXT : 0u) |
+           (d->family >= WSMC_FAM_GAMMA ? WSMC_FEAT_GAM : 0u);
 }
 
 /* ---- the scalar families from WSMC_FAM_BERNOULLI on (src/default_kernels.jl:83-102) -----
@@ -384,9 +389,261 @@ WSMC_HD double wsmc_ext_sample(int fam, double m, double s, uint64_t seed, uint6
     }
 }
 
+/* ---- the log-Gamma families WSMC_FAM_GAMMA .. WSMC_FAM_NEGBINOMIAL ------------------------
+ * first parameter a = mu[0], second b = `scale` (wsmc.h). logpdf: the textbook formulas with
+ * xlogy / xlog1py (0 log 0 = 0), -Inf outside the support (a non-integer x for the discrete
+ * families, as WSMC_FAM_GEOMETRIC), the parameter edges (lambda = 0, p in {0, 1}) written out. */
+WSMC_HD double wsmc_xlogy(double x, double y) { return x == 0.0 ? 0.0 : x * wsmc_log(y); }
+WSMC_HD double wsmc_xlog1py(double x, double y) { return x == 0.0 ? 0.0 : x * wsmc_log1p(y); }
+/* Every family's value is (P + C) + Q with C = wsmc_lgamma3(A1, A2, A3) = (lgamma(A1) -
+ * lgamma(A2)) - lgamma(A3) (an argument 1 contributes its exact 0), so the function holds
+ * wsmc_lgamma's code once:
+ *   Gamma(al, th)    P = xlogy(al - 1, x) - x / th      C = -lgamma(al)           Q = -(al log th)
+ *                    at x = 0: +Inf (al < 1), -log th (al = 1), -Inf (al > 1); at x = +Inf: -Inf
+ *   InverseGamma     P = al log th                      C = -lgamma(al)           Q = -((al + 1) log x + th / x)
+ *   Chisq(nu)        Gamma(nu / 2, 2)
+ *   Beta(al, be)     P = xlogy(al - 1, x) + xlog1py(be - 1, -x)   C = -lbeta(al, be)    Q = 0
+ *   TDist(nu)        P = -((nu + 1)/2 log1p(x^2 / nu))  [x^2 = Inf: 2 log|x| - log nu]  C = lgamma((nu + 1)/2) - lgamma(nu/2)   Q = -(log(nu pi) / 2)
+ *   Poisson(la)      P = xlogy(x, la) - la              C = -lgamma(x + 1)        Q = 0
+ *   Binomial(n, p)   P = xlogy(x, p)                    C = lchoose(n, x)         Q = xlog1py(n - x, -p)
+ *   NegBinomial(r,p) P = r log p       C = (lgamma(r + x) - lgamma(r)) - lgamma(x + 1)   Q = xlog1py(x, -p) */
+WSMC_HD double wsmc_gam_logpdf(int fam, double x, double a, double b, wsmc_logmemo* lm) {
+    double P = 0.0, Q = 0.0, A1 = 1.0, A2 = 1.0, A3 = 1.0;
+    if (x != x) return x;
+    switch (fam) {
+        case WSMC_FAM_GAMMA: case WSMC_FAM_CHISQ: {
+            const int chi = fam == WSMC_FAM_CHISQ;
+            const double al = chi ? 0.5 * a : a, th = chi ? 2.0 : b;
+            const double lth = chi ? WSMC_LOG2 : wsmc_log_memo(lm, b);
+            if (!(x >= 0.0) || x == WSMC_INF) return -WSMC_INF;   /* at +Inf: not (alpha - 1) Inf - Inf */
+            if (x == 0.0) return al < 1.0 ? WSMC_INF : (al == 1.0 ? -lth : -WSMC_INF);
+            P = wsmc_xlogy(al - 1.0, x) - x / th;
+            A2 = al;
+            Q = -(al * lth);
+            break;
+        }
+        case WSMC_FAM_INVERSEGAMMA:
+            if (!(x > 0.0)) return -WSMC_INF;
+            P = a * wsmc_log_memo(lm, b);
+            A2 = a;
+            Q = -((a + 1.0) * wsmc_log(x) + b / x);
+            break;
+        case WSMC_FAM_BETA:
+            if (!(x >= 0.0 && x <= 1.0)) return -WSMC_INF;
+            P = wsmc_xlogy(a - 1.0, x) + wsmc_xlog1py(b - 1.0, -x);
+            A1 = a + b;
+            A2 = a;
+            A3 = b;
+            break;
+        case WSMC_FAM_TDIST: {   /* x^2 past the largest double: log1p(x^2 / nu) as 2 log|x| - log nu */
+            const double xx = x * x;
+            A1 = 0.5 * (a + 1.0);
+            A2 = 0.5 * a;
+            P = -(A1 * (xx < WSMC_INF ? wsmc_log1p(xx / a) : 2.0 * wsmc_log(wsmc_fabs(x)) - wsmc_log(a)));
+            Q = -(0.5 * wsmc_log(a * WSMC_PI));
+            break;
+        }
+        case WSMC_FAM_POISSON:
+            if (!(x >= 0.0 && x == wsmc_floor(x))) return -WSMC_INF;
+            if (a == 0.0) return x == 0.0 ? 0.0 : -WSMC_INF;
+            P = wsmc_xlogy(x, a) - a;
+            A2 = x + 1.0;
+            break;
+        case WSMC_FAM_BINOMIAL:
+            if (!(x >= 0.0 && x <= a && x == wsmc_floor(x))) return -WSMC_INF;
+            if (b == 0.0) return x == 0.0 ? 0.0 : -WSMC_INF;
+            if (b == 1.0) return x == a ? 0.0 : -WSMC_INF;
+            P = wsmc_xlogy(x, b);
+            A1 = a + 1.0;
+            A2 = x + 1.0;
+            A3 = (a - x) + 1.0;
+            Q = wsmc_xlog1py(a - x, -b);
+            break;
+        default:   /* WSMC_FAM_NEGBINOMIAL */
+            if (!(x >= 0.0 && x == wsmc_floor(x))) return -WSMC_INF;
+            if (b == 1.0) return x == 0.0 ? 0.0 : -WSMC_INF;
+            P = a * wsmc_log_memo(lm, b);
+            A1 = a + x;
+            A2 = a;
+            A3 = x + 1.0;
+            Q = wsmc_xlog1py(x, -b);
+            break;
+    }
+    return (P + wsmc_lgamma3(A1, A2, A3)) + Q;
+}
+
+/* Draws. Every rejection loop is bounded: round r of a stage takes its numbers from the Philox
+ * blocks (stage base + r), so a draw is a function of (seed, op, idx) alone, whatever lanes share
+ * a wave, and after the cap the stage returns a fixed in-support value. The stages' block ranges
+ * (disjoint from the normals' 0, 1 and the uniforms' 0x80, 0x81 of the other families):
+ *   Gamma stage at base G: normals G + r, uniforms G + 0x40 + r, the alpha < 1 boost G + 0x7f
+ *   Poisson / Binomial stage at base P: rejection rounds P + r, the inversion uniform P + 0x3f */
+#define WSMC_GAM_BLK_G1 0x100u
+#define WSMC_GAM_BLK_G2 0x180u
+#define WSMC_GAM_BLK_P 0x200u
+/* Marsaglia & Tsang (2000): d = alpha - 1/3, c = 1/(3 sqrt d), v = (1 + c z)^3, accept when
+ * log u < z^2/2 + d - d v + d log v. The acceptance rate is lowest at alpha = 1 (0.951) and
+ * rises to 1: 24 rounds all fail with probability below 0.049^24 < 4e-32; then d is returned
+ * (Gamma(alpha)'s mode + 2/3). alpha < 1: the draw at alpha + 1 times u^(1/alpha) as
+ * exp(log(u) / alpha). Gamma(alpha, 1). */
+#define WSMC_GAMMA_ROUNDS 24
+/* the draw in two parts: the Marsaglia-Tsang value (at alpha + 1 when alpha < 1) returned, and
+ * in *lb the boost's logarithm log(u) / alpha (0 when alpha >= 1); the draw is their product */
+WSMC_HD double wsmc_gamma_parts(double al, uint64_t seed, uint64_t op, uint64_t idx, uint32_t base, double* lb) {
+    const int small = al < 1.0;
+    const double d = (small ? al + 1.0 : al) - 0.33333333333333331;
+    const double c = 0.33333333333333331 / wsmc_sqrt(d);
+    double g = d;
+    for (uint32_t r = 0; r < WSMC_GAMMA_ROUNDS; ++r) {
+        double z, z1;
+        wsmc_normal_pair(wsmc_rng_block(seed, op, idx, base + r), &z, &z1);
+        const double t = 1.0 + c * z;
+        if (!(t > 0.0)) continue;
+        const double v = t * t * t;
+        const wsmc_u32x4 w = wsmc_rng_block(seed, op, idx, base + 0x40u + r);
+        const double u = wsmc_u01_open0(w.v[0], w.v[1]);
+        if (wsmc_log(u) < ((0.5 * z * z + d) - d * v) + d * wsmc_log(v)) {
+            g = d * v;
+            break;
+        }
+    }
+    *lb = 0.0;
+    if (small) {
+        const wsmc_u32x4 w = wsmc_rng_block(seed, op, idx, base + 0x7fu);
+        *lb = wsmc_log(wsmc_u01_open0(w.v[0], w.v[1])) / al;
+    }
+    return g;
+}
+WSMC_HD double wsmc_gamma_draw(double al, uint64_t seed, uint64_t op, uint64_t idx, uint32_t base) {
+    double lb;
+    const double g = wsmc_gamma_parts(al, seed, op, idx, base, &lb);
+    return al < 1.0 ? g * wsmc_exp(lb) : g;
+}
+/* Inversion by sequential search on one uniform, for a mean below 10: k climbs while u is above
+ * the running CDF. The search ends at WSMC_INV_STEPS (P(k > 96) < 1e-50 at mean 10), at the
+ * caller's kmax, or when a term no longer changes the sum (u within rounding of 1). The pmf
+ * ratio is p(k) / p(k - 1) = ra / k + rb: Poisson (lambda, 0), Binomial ((n + 1) s, -s) with
+ * s = p / (1 - p). */
+#define WSMC_INV_STEPS 96
+WSMC_HD double wsmc_invert_draw(double u, double p0, double ra, double rb, double kmax) {
+    double k = 0.0, p = p0, s = p0;
+    for (int j = 0; j < WSMC_INV_STEPS; ++j) {
+        if (!(u > s) || !(k < kmax)) break;
+        k = k + 1.0;
+        p = p * (ra / k + rb);
+        const double s1 = s + p;
+        if (s1 == s) break;
+        s = s1;
+    }
+    return k;
+}
+/* Hörmann (1993) PTRS, transformed rejection with squeeze, for lambda >= 10. The hat's area
+ * is 1 / alpha = 1.1239 + 1.1328 / (b - 3.4) <= 1.33 at lambda = 10 (acceptance 0.75, rising
+ * to 0.89): 60 rounds all fail with probability below 0.25^60 < 1e-36; then floor(lambda). */
+#define WSMC_TRS_ROUNDS 60
+WSMC_HD double wsmc_poisson_draw(double lam, uint64_t seed, uint64_t op, uint64_t idx, uint32_t base) {
+    if (!(lam >= 10.0)) {
+        const wsmc_u32x4 w = wsmc_rng_block(seed, op, idx, base + 0x3fu);
+        return wsmc_invert_draw(wsmc_u01(w.v[0], w.v[1]), wsmc_exp(-lam), lam, 0.0, WSMC_INF);
+    }
+    const double slam = wsmc_sqrt(lam), llam = wsmc_log(lam);
+    const double b = 0.931 + 2.53 * slam;
+    const double a = -0.059 + 0.02483 * b;
+    const double lia = wsmc_log(1.1239 + 1.1328 / (b - 3.4));
+    const double vr = 0.9277 - 3.6224 / (b - 2.0);
+    for (uint32_t r = 0; r < WSMC_TRS_ROUNDS; ++r) {
+        const wsmc_u32x4 w = wsmc_rng_block(seed, op, idx, base + r);
+        const double U = wsmc_u01(w.v[0], w.v[1]) - 0.5, V = wsmc_u01_open0(w.v[2], w.v[3]);
+        const double us = 0.5 - wsmc_fabs(U);
+        const double k = wsmc_floor(((2.0 * a / us + b) * U + lam) + 0.43);
+        if (us >= 0.07 && V <= vr) return k;
+        if (!(k >= 0.0) || (us < 0.013 && V > us)) continue;
+        if ((wsmc_log(V) + lia) - wsmc_log(a / (us * us) + b) <= (k * llam - lam) - wsmc_lgamma(k + 1.0)) return k;
+    }
+    return wsmc_floor(lam);
+}
+/* Binomial(n, p): q = min(p, 1 - p) drawn, n - k returned for p > 1/2. n q < 10: inversion.
+ * Otherwise Hörmann (1993) BTRS; the hat's area is (2.83 + 5.1 / b) / sqrt(2 pi) <= 1.43 at its
+ * worst (n q = 10, q = 1/2: acceptance 0.70): 60 rounds all fail with probability below
+ * 0.30^60 < 1e-31; then the mode floor((n + 1) q). */
+WSMC_HD double wsmc_binomial_draw(double n, double p, uint64_t seed, uint64_t op, uint64_t idx, uint32_t base) {
+    n = wsmc_floor(n);
+    const int flip = p > 0.5;
+    const double q = flip ? 1.0 - p : p;
+    double k;
+    if (!(n * q >= 10.0)) {
+        const wsmc_u32x4 w = wsmc_rng_block(seed, op, idx, base + 0x3fu);
+        const double s = q / (1.0 - q);
+        k = wsmc_invert_draw(wsmc_u01(w.v[0], w.v[1]), wsmc_exp(n * wsmc_log1p(-q)), (n + 1.0) * s, -s, n);
+    } else {
+        const double sd = wsmc_sqrt(n * q * (1.0 - q));
+        const double b = 1.15 + 2.53 * sd;
+        const double a = (-0.0873 + 0.0248 * b) + 0.01 * q;
+        const double c = n * q + 0.5;
+        const double vr = 0.92 - 4.2 / b;
+        const double lal = wsmc_log((2.83 + 5.1 / b) * sd);
+        const double lr = wsmc_log(q / (1.0 - q));
+        const double m = wsmc_floor((n + 1.0) * q);
+        const double hm = -wsmc_lgamma3(1.0, m + 1.0, (n - m) + 1.0);   /* log(m! (n - m)!) */
+        k = m;
+        for (uint32_t r = 0; r < WSMC_TRS_ROUNDS; ++r) {
+            const wsmc_u32x4 w = wsmc_rng_block(seed, op, idx, base + r);
+            const double U = wsmc_u01(w.v[0], w.v[1]) - 0.5, V = wsmc_u01_open0(w.v[2], w.v[3]);
+            const double us = 0.5 - wsmc_fabs(U);
+            const double kk = wsmc_floor((2.0 * a / us + b) * U + c);
+            if (!(kk >= 0.0 && kk <= n)) continue;
+            if (us >= 0.07 && V <= vr) {
+                k = kk;
+                break;
+            }
+            const double lhs = (wsmc_log(V) + lal) - wsmc_log(a / (us * us) + b);
+            if (lhs <= (hm + wsmc_lgamma3(1.0, kk + 1.0, (n - kk) + 1.0)) + (kk - m) * lr) {
+                k = kk;
+                break;
+            }
+        }
+    }
+    return flip ? n - k : k;
+}
+/* one draw of a log-Gamma family (the compound draws' stages on disjoint block ranges) */
+WSMC_HD double wsmc_gam_sample(int fam, double a, double b, uint64_t seed, uint64_t op, uint64_t idx) {
+    switch (fam) {
+        case WSMC_FAM_GAMMA: return b * wsmc_gamma_draw(a, seed, op, idx, WSMC_GAM_BLK_G1);
+        case WSMC_FAM_INVERSEGAMMA: return b / wsmc_gamma_draw(a, seed, op, idx, WSMC_GAM_BLK_G1);
+        case WSMC_FAM_CHISQ: return 2.0 * wsmc_gamma_draw(0.5 * a, seed, op, idx, WSMC_GAM_BLK_G1);
+        case WSMC_FAM_BETA: {
+            double l1, l2;
+            const double c1 = wsmc_gamma_parts(a, seed, op, idx, WSMC_GAM_BLK_G1, &l1);
+            const double c2 = wsmc_gamma_parts(b, seed, op, idx, WSMC_GAM_BLK_G2, &l2);
+            const double g1 = a < 1.0 ? c1 * wsmc_exp(l1) : c1, g2 = b < 1.0 ? c2 * wsmc_exp(l2) : c2;
+            if (g1 >= 9.3326361850321888e-302 && g2 >= 9.3326361850321888e-302) return g1 / (g1 + g2);
+            /* a boost below 2^-1000 or underflowed to 0 (small alpha or beta; both at once 7e-7 a
+               draw at 0.01, 0.01): the same ratio from the logarithms, 1 / (1 + g2 / g1), which
+               keeps a tiny stage's digits against a tinier one, ends at 0 or 1 and is never 0 / 0 */
+            return 1.0 / (1.0 + wsmc_exp((wsmc_log(c2) + l2) - (wsmc_log(c1) + l1)));
+        }
+        case WSMC_FAM_TDIST: {
+            const double z = wsmc_normal_k(seed, op, idx, 0);
+            const double c2 = 2.0 * wsmc_gamma_draw(0.5 * a, seed, op, idx, WSMC_GAM_BLK_G1);
+            return z / wsmc_sqrt(c2 / a);
+        }
+        case WSMC_FAM_POISSON: return wsmc_poisson_draw(a, seed, op, idx, WSMC_GAM_BLK_P);
+        case WSMC_FAM_BINOMIAL: return wsmc_binomial_draw(a, b, seed, op, idx, WSMC_GAM_BLK_P);
+        default: {   /* NegativeBinomial(r, p) = Poisson(Gamma(r, (1 - p) / p)) */
+            const double lam = ((1.0 - b) / b) * wsmc_gamma_draw(a, seed, op, idx, WSMC_GAM_BLK_G1);
+            return wsmc_poisson_draw(lam, seed, op, idx, WSMC_GAM_BLK_P);
+        }
+    }
+}
+
 /* logpdf(D(args...), x) for the supported families */
 WSMC_HD double wsmc_dist_logpdf_mf(const wsmc_dist* d, const double* x, double* const* cols, int64_t N,
                                    int64_t i, const wsmc_override* ov, wsmc_logmemo* lm, unsigned feat) {
+    /* the log-Gamma families are taken before the switch, not as case labels of it: without
+       WSMC_FEAT_GAM (never launched so) the switch is then the one it was, label for label */
+    if ((feat & WSMC_FEAT_GAM) && d->family >= WSMC_FAM_GAMMA)
+        return wsmc_gam_logpdf(d->family, x[0], wsmc_operand_eval(&d->mu[0], cols, N, i, ov),
+                               wsmc_operand_eval(&d->scale, cols, N, i, ov), lm);
     switch (d->family) {
         case WSMC_FAM_NORMAL: {   /* wsmc_normal_logpdf with a remembered log(sigma), 1/sigma */
             double mu = wsmc_dist_mean_f(d, 0, cols, N, i, ov, feat);
@@ -441,6 +698,11 @@ WSMC_HD double wsmc_dist_logpdf(const wsmc_dist* d, const double* x, double* con
  * function of the same bits, so the same result as evaluating it per particle); else null. */
 WSMC_HD void wsmc_dist_sample_mf(const wsmc_dist* d, double* x, uint64_t seed, uint64_t op, uint64_t idx,
                                  double* const* cols, int64_t N, int64_t i, const double* sd_pre, unsigned feat) {
+    if ((feat & WSMC_FEAT_GAM) && d->family >= WSMC_FAM_GAMMA) {   /* as wsmc_dist_logpdf_mf */
+        x[0] = wsmc_gam_sample(d->family, wsmc_operand_eval(&d->mu[0], cols, N, i, 0),
+                               wsmc_operand_eval(&d->scale, cols, N, i, 0), seed, op, idx);
+        return;
+    }
     switch (d->family) {
         case WSMC_FAM_NORMAL: {
             double mu = wsmc_dist_mean_f(d, 0, cols, N, i, 0, feat);

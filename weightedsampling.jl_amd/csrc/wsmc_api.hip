@@ -338,7 +338,9 @@ static int check_operand(const wsmc_ctx* c, const wsmc_operand& o) {
 }
 
 static int check_dist(const wsmc_ctx* c, const wsmc_dist& d) {
-    if (d.family < WSMC_FAM_NORMAL || d.family > WSMC_FAM_GEOMETRIC) return fail(WSMC_EARG, "unknown family");
+    if (d.family < WSMC_FAM_NORMAL || d.family > WSMC_FAM_NEGBINOMIAL ||
+        (d.family > WSMC_FAM_GEOMETRIC && d.family < WSMC_FAM_GAMMA))   // 15 is reserved
+        return fail(WSMC_EARG, "unknown family");
     if (d.dim < 1 || d.dim > 4) return fail(WSMC_EARG, "dist dim must be 1..4");
     if (d.family == WSMC_FAM_MVNORMAL && d.dim > WSMC_MVN_MAXDIM)
         return fail(WSMC_EARG, "MvNormal with a full covariance: dim must be 1..3");
@@ -2553,6 +2555,7 @@ int wsmc_resample(wsmc_ctx* c, double ess_min, int32_t scheme, int32_t* resample
     }
     bool qs_done = false;
     if (fused_rs && c->ew && c->ew->nops > 0 && c->ew->has_w && c->ew_qs_ok && c->rs_qs && run_qstat_mode(c->N) != 0 &&
+        !(c->ew_feat & WSMC_FEAT_GAM) &&   // the statistics' form is two particles a thread (wsmc_jit.hip)
         ew_pair_ok(*c->ew, c->N)) {
         if (!c->run_nfix) {
             WSMC_HIP(hipMalloc(&c->run_nfix, sizeof(unsigned long long)));

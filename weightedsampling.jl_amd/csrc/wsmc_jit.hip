@@ -190,9 +190,19 @@ bool ew_tables_lds(const EwSig& g) {
         if (g.op[k].kind == 1) return true;
     return false;
 }
-std::string tu_source(const std::string& sig, bool lds, bool qs) {
+// a batch with a log-Gamma family runs one particle a thread: two bounded rejection loops
+// unrolled side by side in a lane run one after the other anyway, put the pair's rows in scratch
+// (632 B a lane for a Binomial Sample + Observe) and, for a NegativeBinomial pair, took the
+// compiler down in its post-RA scheduler, which under hiprtc takes the process down with it
+bool ew_single(unsigned feat) { return (feat & WSMC_FEAT_GAM) != 0; }
+std::string tu_source(const std::string& sig, bool lds, bool qs, bool single) {
     const std::string head = std::string(lds ? "#define WSMC_TABLES_LDS 1\n" : "") + "#include \"wsmc_ew_body.h\"\n"
                              "struct WsmcSig { static constexpr wsmc::EwSig sig = " + sig + "; };\n";
+    if (single)
+        return head +
+               "extern \"C\" __global__ __launch_bounds__(256) void wsmc_ew_p1(wsmc::EwBatch, uint64_t seed, int64_t goff, "
+               "int64_t N) { wsmc::ew_body<WsmcSig, 1>(seed, goff, N); }\n"
+               "extern \"C\" __global__ void wsmc_ew_p2(wsmc::EwBatch, uint64_t, int64_t, int64_t) {}\n";
     if (qs)   // the statistics: two particles a thread, 512 threads = one Resample tile a block
         return head +
                "extern \"C\" __global__ void wsmc_ew_p1(wsmc::EwBatch, uint64_t, int64_t, int64_t) {}\n"
@@ -244,8 +254,8 @@ bool compile_src(const std::string& arch, const std::string& src, std::string& c
 }
 
 bool compile_code(const std::string& arch, const std::string& sig, std::string& code, std::string& err, bool lds,
-                  bool qs) {
-    return compile_src(arch, tu_source(sig, lds, qs), code, err);
+                  bool qs, bool single) {
+    return compile_src(arch, tu_source(sig, lds, qs && !single, single), code, err);
 }
 
 bool device_arch(int device, std::string& arch, std::string& err) {
@@ -276,7 +286,7 @@ bool load_module(int device, const std::string& code, const char* f0, const char
     return true;
 }
 
-bool compile(int device, const std::string& sig, JitKernel& out, std::string& err, bool lds, bool qs) {
+bool compile(int device, const std::string& sig, JitKernel& out, std::string& err, bool lds, bool qs, bool single) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) != hipSuccess) {
         err = "hipGetDeviceProperties failed";
@@ -285,7 +295,7 @@ bool compile(int device, const std::string& sig, JitKernel& out, std::string& er
     std::string arch = prop.gcnArchName;   // e.g. "gfx950:sramecc+:xnack-": the processor alone
     arch = arch.substr(0, arch.find(':'));
     std::string code;
-    if (!compile_code(arch, sig, code, err, lds, qs)) return false;
+    if (!compile_code(arch, sig, code, err, lds, qs, single)) return false;
     int cur = 0;
     hipGetDevice(&cur);
     hipSetDevice(device);
@@ -344,7 +354,7 @@ hipError_t launch_ew_jit(hipStream_t s, const EwBatch& b, unsigned feat, uint64_
             JitKernel k;
             std::string err;
             const auto t0 = std::chrono::steady_clock::now();
-            k.ok = compile(device, key, k, err, ew_tables_lds(sg), sg.qs != 0);
+            k.ok = compile(device, key, k, err, ew_tables_lds(sg), sg.qs != 0, ew_single(sg.feat));
             const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
             C.compile_s += dt;
             if (k.ok) {
@@ -364,8 +374,8 @@ hipError_t launch_ew_jit(hipStream_t s, const EwBatch& b, unsigned feat, uint64_
         }
         C.launched += 1;
     }
-    const int P = pair_ok(b, N) ? 2 : 1;
-    if (sg.qs && P != 2) return hipErrorInvalidValue;   // (the caller checked ew_pair_ok)
+    const int P = (pair_ok(b, N) && !ew_single(sg.feat)) ? 2 : 1;
+    if (sg.qs && P != 2) return hipErrorInvalidValue;   // (the caller checked ew_pair_ok and the features)
     const int NT = sg.qs ? 512 : kBlock;
     const int64_t threads = (N + P - 1) / P;
     const unsigned grid = (unsigned)((threads + NT - 1) / NT);
@@ -405,9 +415,46 @@ int ew_jit_selfcheck(std::string& err) {
         }
     }
     std::string code;
-    if (!compile_code("gfx950", sig_text(g), code, err, ew_tables_lds(g), false)) return -1;
+    if (!compile_code("gfx950", sig_text(g), code, err, ew_tables_lds(g), false, false)) return -1;
     g.qs = 1;   // and its form with the Resample statistics
-    return compile_code("gfx950", sig_text(g), code, err, ew_tables_lds(g), true) ? 0 : -1;
+    if (!compile_code("gfx950", sig_text(g), code, err, ew_tables_lds(g), true, false)) return -1;
+    // log-Gamma batches, parameters a, b from columns (rows 0, 1), outputs in rows 2..: Samples of
+    // fam[0 .. ns), then Observes of the same families at those outputs. The shapes: the compound
+    // NegativeBinomial draw scored, Binomial (BTRS, the largest sampler) scored, six Samples a
+    // batch, and every other family once
+    auto gam = [&](const int* fam, int ns, int nobs) {
+        EwSig h;
+        std::memset(&h, 0, sizeof(h));
+        h.nops = (int8_t)(ns + nobs); h.has_w = (int8_t)(nobs > 0); h.npre = 2;
+        h.pre_row[1] = 1;
+        h.feat = WSMC_FEAT_GAM;
+        for (int k = 0; k < ns + nobs; ++k) {
+            EwSigOp& o = h.op[k];
+            std::memset(&o, -1, sizeof(o));
+            o.kind = (int8_t)(k < ns ? 1 : 2);
+            o.dim = 1;
+            o.out_row = (int8_t)(k < ns ? 2 + k : -1);
+            o.family = (int8_t)fam[k < ns ? k : k - ns];
+            o.mean_fn = 0;
+            o.ddim = 1;
+            o.has_sd = o.nostore = 0;
+            for (int q = 0; q < 4; ++q)
+                for (int m = 0; m < 2; ++m) {
+                    o.asrc[q][m] = kSrcNone;
+                    o.arow[q][m] = 0;
+                }
+            o.mrow[0][0] = 0;
+            o.srow[0] = 1;
+            if (k >= ns)
+                for (int q = 0; q < 4; ++q) o.xrow[q][0] = (int8_t)(2 + k - ns);
+        }
+        return compile_code("gfx950", sig_text(h), code, err, ew_tables_lds(h), false, ew_single(h.feat));
+    };
+    const int nb[] = {WSMC_FAM_NEGBINOMIAL}, bi[] = {WSMC_FAM_BINOMIAL};
+    const int six[] = {WSMC_FAM_NEGBINOMIAL, WSMC_FAM_NEGBINOMIAL, WSMC_FAM_BINOMIAL,
+                       WSMC_FAM_BINOMIAL,    WSMC_FAM_POISSON,     WSMC_FAM_BETA};
+    const int rest[] = {WSMC_FAM_GAMMA, WSMC_FAM_INVERSEGAMMA, WSMC_FAM_TDIST};
+    return gam(nb, 1, 1) && gam(bi, 1, 1) && gam(six, 6, 0) && gam(rest, 3, 3) ? 0 : -1;
 }
 
 void ew_jit_stats(int64_t* out) {

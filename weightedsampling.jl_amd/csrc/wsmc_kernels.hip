@@ -278,8 +278,9 @@ __global__ __launch_bounds__(kBlock) void k_assign_expr(XProg) {
         if (k < X->dim) X->out[(int64_t)k * N + i] = res[k];
 }
 
-// FEAT (wsmc_terms.h): WSMC_FEAT_ALL, WSMC_FEAT_OSC, or 0 for affine means (no oscillator or
-// full-covariance code: registers)
+// FEAT (wsmc_terms.h): WSMC_FEAT_BASE, WSMC_FEAT_OSC, or 0 for affine means (no oscillator or
+// full-covariance code: registers); WSMC_FEAT_GAM or WSMC_FEAT_ALL when a log-Gamma family is
+// met, so only those instantiations carry wsmc_lgamma and the rejection samplers
 template <unsigned FEAT>
 __global__ __launch_bounds__(kBlock) void k_sample(double* out, int dim, wsmc_dist d, uint64_t seed,
                                                    uint64_t op, int64_t goff, double* const* cols,
@@ -3812,8 +3813,11 @@ hipError_t launch_sample(hipStream_t s, double* out, int dim, const wsmc_dist& d
                          int64_t goff, double* const* cols, int64_t N) {
     const int has_sd = d.family == WSMC_FAM_MVNORMAL_ISO && wsmc_operand_is_const(&d.scale);
     const double sd = has_sd ? wsmc_sqrt(wsmc_operand_eval(&d.scale, nullptr, N, 0, nullptr)) : 0.0;
-    if (wsmc_dist_feat(&d) & (WSMC_FEAT_MVN | WSMC_FEAT_EXT))
-        hipLaunchKernelGGL(k_sample<WSMC_FEAT_ALL>, grid_for(N), dim3(kBlock), 0, s, out, dim, d, seed, op, goff, cols,
+    if (wsmc_dist_feat(&d) & WSMC_FEAT_GAM)   // a log-Gamma family alone (its mean is never the oscillator)
+        hipLaunchKernelGGL(k_sample<WSMC_FEAT_GAM>, grid_for(N), dim3(kBlock), 0, s, out, dim, d, seed, op, goff, cols,
+                           N, has_sd, sd);
+    else if (wsmc_dist_feat(&d) & (WSMC_FEAT_MVN | WSMC_FEAT_EXT))
+        hipLaunchKernelGGL(k_sample<WSMC_FEAT_BASE>, grid_for(N), dim3(kBlock), 0, s, out, dim, d, seed, op, goff, cols,
                            N, has_sd, sd);
     else if (d.mean_fn == WSMC_MEAN_OSCILLATOR)
         hipLaunchKernelGGL(k_sample<WSMC_FEAT_OSC>, grid_for(N), dim3(kBlock), 0, s, out, dim, d, seed, op, goff, cols,
@@ -3844,8 +3848,10 @@ hipError_t launch_ew_assign1(hipStream_t s, const EwBatch& b, double* const* col
 hipError_t launch_ew_batch(hipStream_t s, const EwBatch& b, unsigned feat, uint64_t seed, int64_t goff, int64_t N) {
     static_assert(sizeof(EwBatch) + 32 <= 4096, "the batch rides in the kernel arguments");
     const size_t rows = sizeof(double) * kBlock * (size_t)b.nrows;   // only the rows used: occupancy
-    if (feat & (WSMC_FEAT_MVN | WSMC_FEAT_EXT))
+    if (feat & WSMC_FEAT_GAM)
         hipLaunchKernelGGL(k_ew_batch<WSMC_FEAT_ALL>, grid_for(N), dim3(kBlock), rows, s, b, seed, goff, N);
+    else if (feat & (WSMC_FEAT_MVN | WSMC_FEAT_EXT))
+        hipLaunchKernelGGL(k_ew_batch<WSMC_FEAT_BASE>, grid_for(N), dim3(kBlock), rows, s, b, seed, goff, N);
     else if (feat)
         hipLaunchKernelGGL(k_ew_batch<WSMC_FEAT_OSC>, grid_for(N), dim3(kBlock), rows, s, b, seed, goff, N);
     else
@@ -3855,8 +3861,15 @@ hipError_t launch_ew_batch(hipStream_t s, const EwBatch& b, unsigned feat, uint6
 hipError_t launch_sample_importance(hipStream_t s, double* out, int dim, const wsmc_dist& prop,
                                     const wsmc_dist& targ, double* w, uint64_t seed, uint64_t op,
                                     int64_t goff, double* const* cols, int64_t N) {
-    if ((wsmc_dist_feat(&prop) | wsmc_dist_feat(&targ)) & (WSMC_FEAT_MVN | WSMC_FEAT_EXT))
+    const unsigned feat = wsmc_dist_feat(&prop) | wsmc_dist_feat(&targ);
+    if (feat == WSMC_FEAT_GAM)   // both of the log-Gamma families
+        hipLaunchKernelGGL(k_sample_importance<WSMC_FEAT_GAM>, grid_for(N), dim3(kBlock), 0, s, out, dim, prop, targ, w,
+                           seed, op, goff, cols, N);
+    else if (feat & WSMC_FEAT_GAM)
         hipLaunchKernelGGL(k_sample_importance<WSMC_FEAT_ALL>, grid_for(N), dim3(kBlock), 0, s, out, dim, prop, targ, w,
+                           seed, op, goff, cols, N);
+    else if (feat & (WSMC_FEAT_MVN | WSMC_FEAT_EXT))
+        hipLaunchKernelGGL(k_sample_importance<WSMC_FEAT_BASE>, grid_for(N), dim3(kBlock), 0, s, out, dim, prop, targ, w,
                            seed, op, goff, cols, N);
     else
         hipLaunchKernelGGL(k_sample_importance<WSMC_FEAT_OSC>, grid_for(N), dim3(kBlock), 0, s, out, dim, prop, targ, w,
@@ -3873,8 +3886,11 @@ hipError_t launch_weigh(hipStream_t s, const wsmc_term& t, double* w, double* co
         lm0.rcp = 1.0 / sc;
         lm0.valid = 1;
     }
-    if (wsmc_dist_feat(&t.dist) & (WSMC_FEAT_MVN | WSMC_FEAT_EXT))
-        hipLaunchKernelGGL(k_weigh<WSMC_FEAT_ALL>, grid_for(N), dim3(kBlock), 0, s, t, w, cols, N, ms, ms_next, lm0,
+    if (wsmc_dist_feat(&t.dist) & WSMC_FEAT_GAM)   // a log-Gamma family alone
+        hipLaunchKernelGGL(k_weigh<WSMC_FEAT_GAM>, grid_for(N), dim3(kBlock), 0, s, t, w, cols, N, ms, ms_next, lm0,
+                           wreset);
+    else if (wsmc_dist_feat(&t.dist) & (WSMC_FEAT_MVN | WSMC_FEAT_EXT))
+        hipLaunchKernelGGL(k_weigh<WSMC_FEAT_BASE>, grid_for(N), dim3(kBlock), 0, s, t, w, cols, N, ms, ms_next, lm0,
                            wreset);
     else if (t.dist.mean_fn == WSMC_MEAN_OSCILLATOR)
         hipLaunchKernelGGL(k_weigh<WSMC_FEAT_OSC>, grid_for(N), dim3(kBlock), 0, s, t, w, cols, N, ms, ms_next, lm0,

@@ -82,7 +82,12 @@ const FAM_NORMAL, FAM_HALFNORMAL, FAM_UNIFORM, FAM_MVNORMAL_ISO, FAM_MVNORMAL =
 # into the kernel's argument tuple (0: none)
 const EXT_FAMILIES = ((:Bernoulli, 5, 1, 0), (:BernoulliLogit, 6, 1, 0), (:Exponential, 7, 0, 1),
                       (:LogNormal, 8, 1, 2), (:Laplace, 9, 1, 2), (:Cauchy, 10, 1, 2), (:Logistic, 11, 1, 2),
-                      (:Gumbel, 12, 1, 2), (:Rayleigh, 13, 0, 1), (:Geometric, 14, 1, 0))
+                      (:Gumbel, 12, 1, 2), (:Rayleigh, 13, 0, 1), (:Geometric, 14, 1, 0),
+                      # the log-Gamma families (15 is reserved): first parameter mu[0], second `scale`.
+                      # Unrun, as the rest of this shim.
+                      (:Gamma, 16, 1, 2), (:InverseGamma, 17, 1, 2), (:Chisq, 18, 1, 0), (:Beta, 19, 1, 2),
+                      (:TDist, 20, 1, 0), (:Poisson, 21, 1, 0), (:Binomial, 22, 1, 2),
+                      (:NegativeBinomial, 23, 1, 2))
 const MEAN_AFFINE = Int32(0)
 const RESAMPLE_STRATIFIED = Int32(0)
 const PROPOSAL_RW, PROPOSAL_AUTORW = Int32(0), Int32(1)

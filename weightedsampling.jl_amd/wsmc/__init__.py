@@ -10,8 +10,9 @@ from . import abi
 from .abi import (PROPOSAL_AUTORW, PROPOSAL_RW, RESAMPLE_MULTINOMIAL, RESAMPLE_STRATIFIED, RESAMPLE_SYSTEMATIC, WSMCError,
                   load_library)
 from .context import Context, device_count
-from .dsl import (Bernoulli, BernoulliLogit, Cauchy, Col, Exponential, Expr, Fx, Geometric, Gumbel, HalfNormal, Kernel,
-                  Laplace, Logistic, LogNormal, MvNormal, Normal, Oscillator, Rayleigh, Uniform)
+from .dsl import (Bernoulli, BernoulliLogit, Beta, Binomial, Cauchy, Chisq, Col, Exponential, Expr, Fx, Gamma, Geometric,
+                  Gumbel, HalfNormal, InverseGamma, Kernel, Laplace, Logistic, LogNormal, MvNormal, NegativeBinomial,
+                  Normal, Oscillator, Poisson, Rayleigh, TDist, Uniform)
 from . import dsl
 from . import models
 from .transformers import (Assign, Cond, FusedSSM2D, HipColumnStore, ImportanceKernel, Loop, Move, Observe,
@@ -19,7 +20,8 @@ from .transformers import (Assign, Cond, FusedSSM2D, HipColumnStore, ImportanceK
                            expectation, importance_kernel, marginal_diversity, resampled, run, sample, score_logpdf)
 
 __all__ = ["abi", "dsl", "Context", "device_count", "Col", "Expr", "Fx", "Bernoulli", "BernoulliLogit", "Cauchy", "Exponential", "Geometric", "Gumbel",
-           "Laplace", "Logistic", "LogNormal", "Rayleigh", "Kernel", "Normal", "MvNormal", "HalfNormal",
+           "Laplace", "Logistic", "LogNormal", "Rayleigh", "Gamma", "InverseGamma", "Chisq", "Beta", "TDist", "Poisson", "Binomial",
+           "NegativeBinomial", "Kernel", "Normal", "MvNormal", "HalfNormal",
            "Uniform", "Oscillator", "models", "load_library", "WSMCError", "RESAMPLE_STRATIFIED",
            "RESAMPLE_SYSTEMATIC", "RESAMPLE_MULTINOMIAL", "PROPOSAL_RW", "PROPOSAL_AUTORW", "Assign", "Cond", "FusedSSM2D",
            "HipColumnStore", "ImportanceKernel", "Loop", "Move", "Observe", "Resample", "RW", "Sample", "Sequence",

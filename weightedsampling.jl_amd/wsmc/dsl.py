@@ -292,6 +292,41 @@ def Geometric(p) -> Kernel:
     return _scalar(abi.FAM_GEOMETRIC, p)
 
 
+def Gamma(alpha=1.0, theta=1.0) -> Kernel:
+    """default_kernels.Gamma(α, θ) — α the shape, θ the scale"""
+    return _scalar(abi.FAM_GAMMA, alpha, theta)
+
+
+def InverseGamma(alpha=1.0, theta=1.0) -> Kernel:
+    """default_kernels.InverseGamma(α, θ) — α the shape, θ the scale"""
+    return _scalar(abi.FAM_INVERSEGAMMA, alpha, theta)
+
+
+def Chisq(nu) -> Kernel:
+    return _scalar(abi.FAM_CHISQ, nu)
+
+
+def Beta(alpha=1.0, beta=1.0) -> Kernel:
+    return _scalar(abi.FAM_BETA, alpha, beta)
+
+
+def TDist(nu) -> Kernel:
+    return _scalar(abi.FAM_TDIST, nu)
+
+
+def Poisson(lam=1.0) -> Kernel:
+    return _scalar(abi.FAM_POISSON, lam)
+
+
+def Binomial(n=1, p=0.5) -> Kernel:
+    return _scalar(abi.FAM_BINOMIAL, n, p)
+
+
+def NegativeBinomial(r=1.0, p=0.5) -> Kernel:
+    """default_kernels.NegativeBinomial(r, p): failures before the r-th success, r > 0 real"""
+    return _scalar(abi.FAM_NEGBINOMIAL, r, p)
+
+
 def MvNormal(mu, cov) -> Kernel:
     """default_kernels.MvNormal(μ, Σ) — Σ is a COVARIANCE (src/default_kernels.jl:93). A scalar
     or Σ = v·I takes the isotropic family (dim ≤ 4); any other constant Σ (dim ≤ 3) takes the
