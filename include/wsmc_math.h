@@ -796,13 +796,20 @@ WSMC_HD double wsmc_lchoose(double n, double k) { return wsmc_lgamma3(n + 1.0, k
 /* draws                                                                      */
 /* ------------------------------------------------------------------------- */
 /* Box–Muller pair from one Philox block: z0 = r cos(2πu2), z1 = r sin(2πu2) */
-WSMC_HD void wsmc_normal_pair_t(wsmc_u32x4 w, double* z0, double* z1, const double* logtab) {
-    double u1 = wsmc_u01_open0(w.v[0], w.v[1]);
-    double u2 = wsmc_u01(w.v[2], w.v[3]);
+/* in two parts, for a kernel that has the first computed while its log table is still on the way:
+ * the head needs the block's words only (u1 and the sine and cosine of 2πu2), the tail the table */
+WSMC_HD void wsmc_normal_pair_head(wsmc_u32x4 w, double* u1, double* s, double* c) {
+    *u1 = wsmc_u01_open0(w.v[0], w.v[1]);
+    wsmc_sincos2pi(wsmc_u01(w.v[2], w.v[3]), s, c);
+}
+WSMC_HD void wsmc_normal_pair_tail(double u1, double s, double c, double* z0, double* z1, const double* logtab) {
     double r = wsmc_sqrt(-2.0 * wsmc_log_t(u1, logtab));
-    double s, c;
-    wsmc_sincos2pi(u2, &s, &c);
     *z0 = r * c; *z1 = r * s;
+}
+WSMC_HD void wsmc_normal_pair_t(wsmc_u32x4 w, double* z0, double* z1, const double* logtab) {
+    double u1, s, c;
+    wsmc_normal_pair_head(w, &u1, &s, &c);
+    wsmc_normal_pair_tail(u1, s, c, z0, z1, logtab);
 }
 WSMC_HD void wsmc_normal_pair(wsmc_u32x4 w, double* z0, double* z1) { wsmc_normal_pair_t(w, z0, z1, WSMC_LOG_TAB); }
 /* k-th standard normal of (op, idx) */

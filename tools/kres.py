@@ -20,6 +20,7 @@ import re
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 LISTING = ROOT / "weightedsampling.jl_amd" / "build" / "wsmc_kernels.resources.txt"
+ISA = LISTING.with_name("wsmc_kernels.s")   # the build's device assembly of csrc/wsmc_kernels.hip
 CUS = 256               # MI355X
 SIMDS_PER_CU = 4
 VGPRS_PER_SIMD = 512    # per lane, wave64 (unified with the AGPRs)
@@ -77,13 +78,46 @@ def find(res: dict, *parts: str) -> dict:
     return res[hit[0]]
 
 
+_VMEM_LOAD = re.compile(r"(global|buffer|flat|scratch)_load_\w+")
+
+
+def isa_events(*parts: str, path=ISA) -> list:
+    """The memory schedule of the one kernel whose mangled name holds every part, in the order of
+    the assembly text: ("load", text) for each vector-memory load, ("wait", text) for each
+    s_waitcnt that names vmcnt, ("mad", text) for each v_mad_u64_u32 (a Philox round has two)."""
+    lines = pathlib.Path(path).read_text().splitlines()
+    heads = [(i, ln.split(":", 1)[0]) for i, ln in enumerate(lines)
+             if ln.startswith("_Z") and ":" in ln and all(p in ln.split(":", 1)[0] for p in parts)]
+    if len(heads) != 1:
+        raise KeyError(f"{parts}: {len(heads)} kernels match")
+    out = []
+    for ln in lines[heads[0][0] + 1:]:
+        if ln.startswith(".Lfunc_end"):
+            break
+        t = ln.split(";", 1)[0].strip()
+        op = t.split(None, 1)[0] if t else ""
+        if _VMEM_LOAD.fullmatch(op):
+            out.append(("load", t))
+        elif op == "s_waitcnt" and "vmcnt(" in t:
+            out.append(("wait", t))
+        elif op == "v_mad_u64_u32":
+            out.append(("mad", t))
+    return out
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--listing", default=str(LISTING))
     ap.add_argument("--block", type=int, default=256, help="threads a block")
     ap.add_argument("--blocks", type=int, default=0, help="blocks of the launch: prints its rounds")
     ap.add_argument("parts", nargs="*", help="print the kernels whose mangled name holds one of these")
+    ap.add_argument("--isa", action="store_true", help="print the loads, vmcnt waits and 64-bit multiplies of the one "
+                    "kernel whose name holds every part, in order")
     a = ap.parse_args()
+    if a.isa:
+        for kind, text in isa_events(*a.parts):
+            print(f"{kind:5s} {text}")
+        return
     for name, r in parse(a.listing).items():
         if a.parts and not any(p in name for p in a.parts):
             continue

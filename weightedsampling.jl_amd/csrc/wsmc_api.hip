@@ -692,7 +692,9 @@ int wsmc_create(wsmc_ctx** out, int64_t n_particles, int32_t device, uint64_t se
 #define ALLOC(ptr, bytes)                                          \
     if (e == hipSuccess) e = hipMalloc((void**)&(ptr), (bytes));
     e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    ALLOC(c->w, sizeof(double) * c->N);
+    // w and qbuf in whole quads: the fill's tile blocks and the fused propagate load them 16 B
+    // at a time from a clamped index, so a ragged last quad (or pair) still lies inside
+    ALLOC(c->w, sizeof(double) * ((c->N + 3) & ~(int64_t)3));
     ALLOC(c->anc, sizeof(int32_t) * c->N);
     ALLOC(c->tmp, sizeof(double) * 4 * c->N);
     ALLOC(c->xchg, sizeof(unsigned long long) * 16 * kMaxWorld);
@@ -703,7 +705,7 @@ int wsmc_create(wsmc_ctx** out, int64_t n_particles, int32_t device, uint64_t se
     ALLOC(c->mslots, sizeof(MaxSlots));
     ALLOC(c->wslots[0], sizeof(MaxSlots));
     ALLOC(c->wslots[1], sizeof(MaxSlots));
-    ALLOC(c->qbuf, sizeof(unsigned long long) * c->N);
+    ALLOC(c->qbuf, sizeof(unsigned long long) * ((c->N + 3) & ~(int64_t)3));
     ALLOC(c->tilepart, sizeof(double) * 64 * c->ntiles);   // a Move block's per-move moment sets
     ALLOC(c->rec, sizeof(ShardRecord) * kMaxWorld);
     ALLOC(c->dec, sizeof(Decision));

@@ -105,6 +105,37 @@ __device__ __forceinline__ double wave_sum_f64_exact(double v) {
     v = v + dpp_f64<kDppBcast31>(v);
     return __builtin_bit_cast(double, lane63_u64(__builtin_bit_cast(u64, v)));
 }
+// Wave totals of four such values at once, transposing: the two halves of the wave, then the two
+// rows of each half, exchange one of two live values and add (v_permlane32_swap, v_permlane16_swap),
+// which leaves one value a lane, the partial of v[r] in row r; four steps inside the rows finish
+// it. 14 lane moves and 7 additions where four wave_sum_f64_exact take 48 and 24. Every lane of
+// row r (lanes 16 r .. 16 r + 15) returns the total of v[r].
+__device__ __forceinline__ void lane_swap32(double& a, double& b) {   // a's upper half <-> b's lower half
+    const u64 x = __builtin_bit_cast(u64, a), y = __builtin_bit_cast(u64, b);
+    const auto lo = __builtin_amdgcn_permlane32_swap((uint32_t)x, (uint32_t)y, false, false);
+    const auto hi = __builtin_amdgcn_permlane32_swap((uint32_t)(x >> 32), (uint32_t)(y >> 32), false, false);
+    a = __builtin_bit_cast(double, ((u64)hi[0] << 32) | lo[0]);
+    b = __builtin_bit_cast(double, ((u64)hi[1] << 32) | lo[1]);
+}
+__device__ __forceinline__ void lane_swap16(double& a, double& b) {   // a's odd rows <-> b's even rows
+    const u64 x = __builtin_bit_cast(u64, a), y = __builtin_bit_cast(u64, b);
+    const auto lo = __builtin_amdgcn_permlane16_swap((uint32_t)x, (uint32_t)y, false, false);
+    const auto hi = __builtin_amdgcn_permlane16_swap((uint32_t)(x >> 32), (uint32_t)(y >> 32), false, false);
+    a = __builtin_bit_cast(double, ((u64)hi[0] << 32) | lo[0]);
+    b = __builtin_bit_cast(double, ((u64)hi[1] << 32) | lo[1]);
+}
+__device__ __forceinline__ double wave_sum4_f64_exact(double v0, double v1, double v2, double v3) {
+    lane_swap32(v0, v2);            // lower half: v0 of both halves; upper half: v2 of both
+    lane_swap32(v1, v3);
+    double a = v0 + v2, b = v1 + v3;
+    lane_swap16(a, b);              // rows 0..3 of a: v0, v1, v2, v3 (two rows each); b: the other rows
+    double r = a + b;
+    r = r + dpp_f64<kDppQuad1032>(r);
+    r = r + dpp_f64<kDppQuad2301>(r);
+    r = r + dpp_f64<kDppRowRor4>(r);
+    r = r + dpp_f64<kDppRowRor8>(r);
+    return r;
+}
 // inclusive prefix sum over the wave (lane order)
 __device__ __forceinline__ u64 wave_incl_scan_u64(u64 v) {
     u64 x = v + dpp_u64<kDppRowShr1>(v);
@@ -1204,13 +1235,20 @@ __device__ __forceinline__ double wave_incl_scan_f64(double v) {
 
 // the tile's q in registers (4 blocked particles a thread) as exact doubles, and the thread's
 // inclusive local prefixes (exact: a tile's sum is at most 2^53)
+// Two 16-B loads under no branch (a load under its own `i < N` branch is waited for at the
+// branch's join, one round trip a value): qbuf and the weights are allocated in whole quads
+// (wsmc_create), so the quad at i < N lies inside the buffer; threads past N read quad 0, and
+// the entries past N are selected away after the load.
 template <int IT>
 __device__ __forceinline__ void load_tile_q(int64_t N, int b, const u64* __restrict__ qbuf, u64 (&q)[IT]) {
-#pragma unroll
-    for (int k = 0; k < IT; ++k) {
-        const int64_t i = (int64_t)b * kRsTile + (int64_t)threadIdx.x * IT + k;
-        q[k] = i < N ? qbuf[i] : 0ull;
-    }
+    static_assert(IT == 4, "one quad a thread");
+    const int64_t i = (int64_t)b * kRsTile + (int64_t)threadIdx.x * IT;
+    const ulonglong2* p = reinterpret_cast<const ulonglong2*>(qbuf + (i < N ? i : 0));
+    const ulonglong2 lo = p[0], hi = p[1];
+    q[0] = i < N ? lo.x : 0ull;
+    q[1] = i + 1 < N ? lo.y : 0ull;
+    q[2] = i + 2 < N ? hi.x : 0ull;
+    q[3] = i + 3 < N ? hi.y : 0ull;
 }
 
 // the same q recomputed from the log-weights against the reference point (the fused run's fill
@@ -1220,12 +1258,15 @@ __device__ __forceinline__ void load_tile_q(int64_t N, int b, const u64* __restr
 template <int IT>
 __device__ __forceinline__ void load_tile_qw(int64_t N, int b, const double* __restrict__ w,
                                              const MaxSlots* __restrict__ ms, const double* rref, u64 (&q)[IT]) {
+    static_assert(IT == 4, "one quad a thread");
+    const int64_t i = (int64_t)b * kRsTile + (int64_t)threadIdx.x * IT;
+    const d2* p = reinterpret_cast<const d2*>(w + (i < N ? i : 0));   // load_tile_q's loads
+    const d2 lo = p[0], hi = p[1];
     double lw[IT];
-#pragma unroll
-    for (int k = 0; k < IT; ++k) {
-        const int64_t i = (int64_t)b * kRsTile + (int64_t)threadIdx.x * IT + k;
-        lw[k] = i < N ? w[i] : -WSMC_INF;
-    }
+    lw[0] = i < N ? lo.x : -WSMC_INF;
+    lw[1] = i + 1 < N ? lo.y : -WSMC_INF;
+    lw[2] = i + 2 < N ? hi.x : -WSMC_INF;
+    lw[3] = i + 3 < N ? hi.y : -WSMC_INF;
     const double R = rref ? *rref : wsmc_qref(wave_slots_max(ms));
     const double sK = wsmc_pow2i(wsmc_qbits((uint64_t)N));
 #pragma unroll
@@ -1968,13 +2009,20 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(WSMC
     const uint64_t opx = op_eff(plan.op, plan.op_dev);
     if (t < ntiles) {
         // ---- first chunk of tile t (its q loads in flight while the offset is summed) ----
+        const u64 qb = plan.tilep[(int64_t)t * kPart];
+        const int g = t / G;
+        // The thread's first group line and first tile partial before this one in its group, from
+        // clamped addresses and selected after: with the q (or weight) quads and qb these are all
+        // of the block's loads while ngroups and G are at most kScanBlock (256M particles), all
+        // independent and issued here ahead of the first wait. The loops take the rare remainder.
+        const u64 g0 = grp[(int64_t)(th < ngroups ? th : 0) * 8];
+        const int bf = g * G + th;
+        const u64 p0 = plan.tilep[(int64_t)(bf < t ? bf : t) * kPart];
         u64 q[kRsTile / kScanBlock];
         if (QW)
             load_tile_qw(N, t, wq, ms, plan.rg_check, q);
         else
             load_tile_q(N, t, qbuf, q);
-        const u64 qb = plan.tilep[(int64_t)t * kPart];   // every load of the block is issued here
-        const int g = t / G;
         u64 pre = 0, tot = 0;
         if (plan.xlines) {   // exact shards: the global Q; the lower ranks' Q, then this rank's groups before
             const int ngw = (int)(plan.xstride / kGroupLine);
@@ -1985,13 +2033,16 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(WSMC
                 pre += (r < plan.dx_rank || (r == plan.dx_rank && kk < g)) ? v : 0ull;
             }
         } else {
-            for (int k = th; k < ngroups; k += kScanBlock) {
+            tot = th < ngroups ? g0 : 0ull;
+            pre = th < g ? g0 : 0ull;
+            for (int k = th + kScanBlock; k < ngroups; k += kScanBlock) {
                 const u64 v = grp[(int64_t)k * 8];
                 tot += v;
                 pre += k < g ? v : 0ull;
             }
         }
-        for (int b = g * G + th; b < t; b += kScanBlock) pre += plan.tilep[(int64_t)b * kPart];
+        pre += bf < t ? p0 : 0ull;
+        for (int b = bf + kScanBlock; b < t; b += kScanBlock) pre += plan.tilep[(int64_t)b * kPart];
         fill_clear(sh);
         // one barrier for the tile's CDF offset, the total Q and the scan of its q
         const int lane = th & 63, wv = th >> 6;
@@ -2036,8 +2087,12 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(WSMC
     qmax = block_max_u64(qmax, s_u);
     block_sum2_u64(Q, cbase, s_red);
     const uint64_t Nr = plan.n_global ? plan.n_global : (uint64_t)N;
-    const double ratio = Q ? wsmc_u64_to_d(Nr) / wsmc_u64_to_d(Q) : 0.0;
-    if (ovf_chunks(qmax, ratio) == 0) return;   // no tile owns more than its first chunk
+    const double ratio_v = Q ? wsmc_u64_to_d(Nr) / wsmc_u64_to_d(Q) : 0.0;
+    if (ovf_chunks(qmax, ratio_v) == 0) return;   // no tile owns more than its first chunk
+    // the same in every thread: held in scalar registers over the chunk loop below (as Q is), whose
+    // fills leave no vector register free for it
+    const double ratio = __builtin_bit_cast(double, ((u64)__builtin_amdgcn_readfirstlane((int)(__builtin_bit_cast(u64, ratio_v) >> 32)) << 32) |
+                                                        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)__builtin_bit_cast(u64, ratio_v)));
 
     const int per = (ntiles + kScanBlock - 1) / kScanBlock;
     const int b0 = th * per < ntiles ? th * per : ntiles;
@@ -3271,6 +3326,10 @@ __device__ __forceinline__ double aff2(double a, double b) {
 // The loads at the head of the block's dependent chain (the ancestor pair, the previous decision,
 // the previous max slots) are issued before the log table is staged, so the table's round trip
 // and its barrier overlap them instead of preceding them.
+// QS (round 8): the part of the draws that needs neither loaded data nor the table is computed
+// under that first round trip, the rest after the gathers are issued, and every gather is a load
+// under no branch, so no wait that covers a gather precedes the last draw instruction
+// (tests/test_kernel_isa.py reads that order from the saved assembly).
 template <int MODE, int IT = 1, int NT = kBlock, bool QS = false, bool ISL = false>
 __global__ __launch_bounds__(NT) void k_ssm2d_prop(Ssm2dArgs a) {
     WSMC_BLK_CLOCK(QS ? 0 : 3);
@@ -3320,19 +3379,51 @@ __global__ __launch_bounds__(NT) void k_ssm2d_prop(Ssm2dArgs a) {
         }
     }
     const uint64_t op_dv = a.op_dev[0] + 3ull * (uint64_t)(a.t - 1);
-    const double o0 = a.obs[2 * (a.t - 1)], o1 = a.obs[2 * (a.t - 1) + 1];
     bool rs = false;
     double mean = 0.0;
     if (!isl && !first) {
         rs = a.dec_prev->resampled;
         mean = rs ? a.dec_prev->mean : 0.0;
     }
-    if (WSMC_PROP_LDS_LOG && (MODE & 1) == 0) {   // every thread, before the first draw
+    // QS: what the draws need of neither loaded data nor the table (the Philox block, the two
+    // uniforms, the sine and cosine, for both particles) is computed here, under the round trip of
+    // the loads above and of the thread's table entry: that entry is loaded first, under no branch,
+    // and staged only after them (by every thread: 2 * WSMC_LOG_TABLE_N <= NT, so two threads
+    // store the same bits to one entry; a store under `th < 256` would take the load into its
+    // branch, behind the draws). The rest of the draws (log, square root, scaling) follows the
+    // barrier and the gathers' issue. The empty asm statements pin the values where they are
+    // written (the optimiser otherwise sinks the whole draw into the `ok` block below, behind the
+    // wait for the gathers), and the scheduling barriers hold the order inside the block.
+    // The operands that only the arithmetic and the stores after the barrier use (ARG_LATE, the
+    // observation) are then read from the kernel's argument segment at an offset the asm below
+    // hands back (0): scalar loads the compiler cannot hoist above the draws, where, held beside
+    // the Philox key schedule, they took the kernel past 80 scalar registers.
+    constexpr bool kSplitDraw = QS && IT == 1 && WSMC_PROP_LDS_LOG && (MODE & 1) == 0 && 2 * WSMC_LOG_TABLE_N <= NT;
+    double du1[2] = {0.0, 0.0}, dsn[2] = {0.0, 0.0}, dcs[2] = {0.0, 0.0};
+    uint32_t koff = 0;
+    if (kSplitDraw) {
+        const double tv = wsmc_log_table()[threadIdx.x & (2 * WSMC_LOG_TABLE_N - 1)];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+            wsmc_normal_pair_head(wsmc_rng_block(a.seed, op_dv, (uint64_t)(a.goff + ib + k), 0u), &du1[k], &dsn[k], &dcs[k]);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) asm volatile("" : "+v"(du1[k]), "+v"(dsn[k]), "+v"(dcs[k]));
+        asm volatile("" : "+s"(koff));
+        __builtin_amdgcn_sched_barrier(0);
+        s_logtab[threadIdx.x & (2 * WSMC_LOG_TABLE_N - 1)] = tv;
+    } else if (WSMC_PROP_LDS_LOG && (MODE & 1) == 0) {   // every thread, before the first draw
         const double* lt = wsmc_log_table();
         for (int k = (int)threadIdx.x; k < 2 * WSMC_LOG_TABLE_N; k += NT) s_logtab[k] = lt[k];
     }
     if ((WSMC_PROP_LDS_LOG && (MODE & 1) == 0) || isl) __syncthreads();   // the table and the island decision
     const double* logtab = WSMC_PROP_LDS_LOG ? s_logtab : wsmc_log_table();
+    typedef const char __attribute__((address_space(4)))* KargBytes;
+    typedef const Ssm2dArgs __attribute__((address_space(4)))* KargP;
+    const KargP ka = (KargP)((KargBytes)__builtin_amdgcn_kernarg_segment_ptr() + koff);
+#define ARG_LATE(f) (kSplitDraw ? ka->f : a.f)
+    const double* const obs_t = ARG_LATE(obs) + 2 * (a.t - 1);
+    const double o0 = obs_t[0], o1 = obs_t[1];
     if (isl) {
         rs = s_dec.resampled;
         mean = rs ? s_dec.mean : 0.0;
@@ -3350,14 +3441,31 @@ __global__ __launch_bounds__(NT) void k_ssm2d_prop(Ssm2dArgs a) {
     for (int j = 0; j < IT; ++j) {
         const int64_t i0 = ib + (int64_t)j * stride;
         wb[j][0] = wb[j][1] = mean;
+        if (QS) {
+            // every load under no lane's branch (its join would wait for the load), from a clamped
+            // index: threads past N and a ragged second particle read particle 0, and the weights
+            // are allocated in whole quads. Their stores stay guarded. The weights are read only
+            // when the previous step did not resample (the same for every thread).
+            if (!rs) {
+                const d2 w2 = *reinterpret_cast<const d2*>(ARG_LATE(w) + (ok[j] ? i0 : 0));
+                wb[j][0] = w2.x; wb[j][1] = w2.y;
+            }
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int64_t sk = (k == 0 ? ok[j] : two[j]) ? src[j][k] : 0;
+                xp[j][k] = *reinterpret_cast<const d2*>(ARG_LATE(x_prev) + 2 * sk);
+                vp[j][k] = *reinterpret_cast<const d2*>(ARG_LATE(v_prev) + 2 * sk);
+            }
+            continue;
+        }
         if (!ok[j]) continue;
         if (!rs) {
             if (two[j]) {
-                const d2 w2 = *reinterpret_cast<const d2*>(a.w + i0);
+                const d2 w2 = *reinterpret_cast<const d2*>(ARG_LATE(w) + i0);
                 wb[j][0] = w2.x; wb[j][1] = w2.y;
                 if (!QS && a.w_save) *reinterpret_cast<d2*>(a.w_save + i0) = w2;
             } else {
-                wb[j][0] = a.w[i0];
+                wb[j][0] = ARG_LATE(w)[i0];
                 if (!QS && a.w_save) a.w_save[i0] = wb[j][0];
             }
         }
@@ -3370,13 +3478,13 @@ __global__ __launch_bounds__(NT) void k_ssm2d_prop(Ssm2dArgs a) {
                 if (MODE & 16) {   // exact shards: global ids; a neighbour's particle arrived at the slot
                     const int64_t loc = rs ? src[j][k] - a.goff : src[j][k];
                     const bool here = loc >= 0 && loc < N;
-                    const double* xs = here ? a.x_prev + 2 * loc : a.xr + 2 * (i0 + k);
-                    const double* vs = here ? a.v_prev + 2 * loc : a.vr + 2 * (i0 + k);
+                    const double* xs = here ? ARG_LATE(x_prev) + 2 * loc : a.xr + 2 * (i0 + k);
+                    const double* vs = here ? ARG_LATE(v_prev) + 2 * loc : a.vr + 2 * (i0 + k);
                     xp[j][k] = *reinterpret_cast<const d2*>(xs);
                     vp[j][k] = *reinterpret_cast<const d2*>(vs);
                 } else {
-                    xp[j][k] = *reinterpret_cast<const d2*>(a.x_prev + 2 * src[j][k]);
-                    vp[j][k] = *reinterpret_cast<const d2*>(a.v_prev + 2 * src[j][k]);
+                    xp[j][k] = *reinterpret_cast<const d2*>(ARG_LATE(x_prev) + 2 * src[j][k]);
+                    vp[j][k] = *reinterpret_cast<const d2*>(ARG_LATE(v_prev) + 2 * src[j][k]);
                 }
             }
         }
@@ -3387,18 +3495,28 @@ __global__ __launch_bounds__(NT) void k_ssm2d_prop(Ssm2dArgs a) {
     if (QS) {
         // the guess: every weight of this step is wb + lp <= base + lpmax (lp <= -c0/2, wb <= base)
         const double base = rs ? mean : wsmc_ord_dec(wave_max_u64(mprev));
-        const double lpmax = -(a.c0 + 0.0) * 0.5;
+        const double lpmax = -(ARG_LATE(c0) + 0.0) * 0.5;
         Rg = wsmc_qref(base + lpmax);
         sK = wsmc_pow2i(wsmc_qbits((uint64_t)N));
-        if (blockIdx.x == 0 && threadIdx.x == 0) *a.rg_out = Rg;
+        if (blockIdx.x == 0 && threadIdx.x == 0) *ARG_LATE(rg_out) = Rg;
+    }
+    double zs[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+    if (kSplitDraw) {   // the draws' second part, with the gathers in flight
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) wsmc_normal_pair_tail(du1[k], dsn[k], dcs[k], &zs[k][0], &zs[k][1], logtab);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) asm volatile("" : "+v"(zs[k][0]), "+v"(zs[k][1]));
+        __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
     for (int j = 0; j < IT; ++j) {
         if (!ok[j]) continue;
         const int64_t i0 = ib + (int64_t)j * stride;
-        // the draws need no loaded data: computed while the gathers are in flight
-        double z[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
-        if ((MODE & 1) == 0) {
+        // the draws need no gathered data. QS: taken above, around the table's barrier (the
+        // compiler schedules these, written here, after the wait for the gathers)
+        double z[2][2] = {{zs[0][0], zs[0][1]}, {zs[1][0], zs[1][1]}};
+        if (!kSplitDraw && (MODE & 1) == 0) {
 #pragma unroll
             for (int k = 0; k < 2; ++k)
                 wsmc_normal_pair_t(wsmc_rng_block(a.seed, op_dv, (uint64_t)(a.goff + i0 + k), 0u), &z[k][0], &z[k][1],
@@ -3411,7 +3529,7 @@ __global__ __launch_bounds__(NT) void k_ssm2d_prop(Ssm2dArgs a) {
             // x{t+1} .= x{t} + v
             const double xn0 = aff2(xp[j][k].x, vp[j][k].x), xn1 = aff2(xp[j][k].y, vp[j][k].y);
             // dv ~ MvNormal([0,0], q*I)
-            const double dv0 = 0.0 + a.q_sd * z[k][0], dv1 = 0.0 + a.q_sd * z[k][1];
+            const double dv0 = 0.0 + ARG_LATE(q_sd) * z[k][0], dv1 = 0.0 + ARG_LATE(q_sd) * z[k][1];
             // v .= v + dv
             const double vn0 = aff2(vp[j][k].x, dv0), vn1 = aff2(vp[j][k].y, dv1);
             // o => MvNormal(x{t+1}, r*I)
@@ -3420,31 +3538,31 @@ __global__ __launch_bounds__(NT) void k_ssm2d_prop(Ssm2dArgs a) {
             const double d0 = o0 - m0, d1 = o1 - m1;
             s = s + d0 * d0;
             s = s + d1 * d1;
-            const double lp = -(a.c0 + s / a.r_var) * 0.5;
+            const double lp = -(ARG_LATE(c0) + s / ARG_LATE(r_var)) * 0.5;
             wn[k] = wb[j][k] + lp;
             xn[k] = d2{xn0, xn1};
             vn[k] = d2{vn0, vn1};
             dvv[k] = d2{dv0, dv1};
         }
-        *reinterpret_cast<d2*>(a.x_next + 2 * i0) = xn[0];
-        *reinterpret_cast<d2*>(a.v_next + 2 * i0) = vn[0];
-        if (a.dv) *reinterpret_cast<d2*>(a.dv + 2 * i0) = dvv[0];
+        *reinterpret_cast<d2*>(ARG_LATE(x_next) + 2 * i0) = xn[0];
+        *reinterpret_cast<d2*>(ARG_LATE(v_next) + 2 * i0) = vn[0];
+        if (ARG_LATE(dv)) *reinterpret_cast<d2*>(ARG_LATE(dv) + 2 * i0) = dvv[0];
         u64 e0 = wsmc_ord_enc(wn[0]);
         menc = e0 > menc ? e0 : menc;
         u64 q0 = 0, q1 = 0;
         if (QS) q0 = qacc_add(acc, wsmc_expw(wn[0] - Rg), sK);
         if (two[j]) {
-            *reinterpret_cast<d2*>(a.x_next + 2 * i0 + 2) = xn[1];
-            *reinterpret_cast<d2*>(a.v_next + 2 * i0 + 2) = vn[1];
-            if (a.dv) *reinterpret_cast<d2*>(a.dv + 2 * i0 + 2) = dvv[1];
-            *reinterpret_cast<d2*>(a.w + i0) = d2{wn[0], wn[1]};
+            *reinterpret_cast<d2*>(ARG_LATE(x_next) + 2 * i0 + 2) = xn[1];
+            *reinterpret_cast<d2*>(ARG_LATE(v_next) + 2 * i0 + 2) = vn[1];
+            if (ARG_LATE(dv)) *reinterpret_cast<d2*>(ARG_LATE(dv) + 2 * i0 + 2) = dvv[1];
+            *reinterpret_cast<d2*>(ARG_LATE(w) + i0) = d2{wn[0], wn[1]};
             const u64 e1 = wsmc_ord_enc(wn[1]);
             menc = e1 > menc ? e1 : menc;
             if (QS) q1 = qacc_add(acc, wsmc_expw(wn[1] - Rg), sK);
-            if (QS && a.qbuf) *reinterpret_cast<ulonglong2*>(a.qbuf + i0) = make_ulonglong2(q0, q1);
+            if (QS && ARG_LATE(qbuf)) *reinterpret_cast<ulonglong2*>(ARG_LATE(qbuf) + i0) = make_ulonglong2(q0, q1);
         } else {
-            a.w[i0] = wn[0];
-            if (QS && a.qbuf) a.qbuf[i0] = q0;
+            ARG_LATE(w)[i0] = wn[0];
+            if (QS && ARG_LATE(qbuf)) ARG_LATE(qbuf)[i0] = q0;
         }
     }
     if (QS) {
@@ -3452,25 +3570,20 @@ __global__ __launch_bounds__(NT) void k_ssm2d_prop(Ssm2dArgs a) {
         // of k_rs_sums_t)
         __shared__ double s_f[kPart][NT / 64];
         const int th = threadIdx.x, wv = th >> 6;
-        acc.Q = wave_sum_f64_exact(acc.Q);
-        acc.Q2 = wave_sum_f64_exact(acc.Q2);
-        acc.WF2 = wave_sum_f64_exact(acc.WF2);
-        acc.WF = wave_sum_f64_exact(acc.WF);
+        // exact integers below 2^53: any order of additions gives the same bits
+        const double part = wave_sum4_f64_exact(acc.Q, acc.Q2, acc.WF2, acc.WF);
         menc = wave_max_u64(menc);
-        if ((th & 63) == 0) {
-            s_f[0][wv] = acc.Q; s_f[1][wv] = acc.Q2;
-            s_f[2][wv] = acc.WF2; s_f[3][wv] = acc.WF;
-            lds4[wv] = menc;
-        }
+        if ((th & 15) == 0) s_f[(th & 63) >> 4][wv] = part;   // row r holds partial r
+        if ((th & 63) == 0) lds4[wv] = menc;
         __syncthreads();
         if (th < kPart) {
             double f = 0.0;
 #pragma unroll
             for (int v = 0; v < NT / 64; ++v) f = f + s_f[th][v];
             const u64 t = (u64)f;                     // exact integer <= 2^53
-            a.tilep[(int64_t)blockIdx.x * kPart + th] = t;
+            ARG_LATE(tilep)[(int64_t)blockIdx.x * kPart + th] = t;
             if (th == 0) {
-                u64* gl = a.grp + (int64_t)(blockIdx.x / a.G) * kGroupLine;
+                u64* gl = ARG_LATE(grp) + (int64_t)(blockIdx.x / ARG_LATE(G)) * kGroupLine;
                 atomicAdd(gl, t);
                 atomicMax(gl + 1, t);
             }
@@ -3478,22 +3591,23 @@ __global__ __launch_bounds__(NT) void k_ssm2d_prop(Ssm2dArgs a) {
             u64 m = 0;
 #pragma unroll
             for (int v = 0; v < NT / 64; ++v) m = lds4[v] > m ? lds4[v] : m;
-            atomic_max_filtered(&a.ms->v[blockIdx.x % kSlots][0], m);
+            atomic_max_filtered(&ARG_LATE(ms)->v[blockIdx.x % kSlots][0], m);
         }
         return;
     }
     if (MODE & 4) {                                  // diag: no block max / atomic
-        if (menc == 0x123456789ull) a.w[0] = 0.0;
+        if (menc == 0x123456789ull) ARG_LATE(w)[0] = 0.0;
         return;
     }
     if (MODE & 8) {                                  // diag: wave max + unfiltered atomic per wave
         menc = wave_max_u64(menc);
-        if ((threadIdx.x & 63) == 0) atomicMax(&a.ms->v[(blockIdx.x * 4 + (threadIdx.x >> 6)) % kSlots][0], menc);
+        if ((threadIdx.x & 63) == 0) atomicMax(&ARG_LATE(ms)->v[(blockIdx.x * 4 + (threadIdx.x >> 6)) % kSlots][0], menc);
         return;
     }
     menc = block_max_u64(menc, lds4);
-    if (threadIdx.x == 0) atomic_max_filtered(&a.ms->v[blockIdx.x % kSlots][0], menc);
+    if (threadIdx.x == 0) atomic_max_filtered(&ARG_LATE(ms)->v[blockIdx.x % kSlots][0], menc);
 }
+#undef ARG_LATE
 
 // ---- exact-sharded fused run: distributed trace-back -------------------
 // words per global index: x pair (2 doubles) + the ancestor id of the step before
