@@ -203,6 +203,16 @@ static void virt_drop(wsmc_ctx* c, int32_t col) {
             }
 }
 
+// launch the open batch on behalf of a statement that reads `reads`: the batch's unstored Sample
+// outputs become VirtCol entries only now, after the statement looked for its operands among
+// them (virt_one), and it will read them from memory, not from the launched batch's rows
+static int ew_flush_reads(wsmc_ctx* c, const std::vector<int32_t>& reads) {
+    if (int r = ew_flush(c)) return r;
+    for (int32_t id : reads)
+        if (int r = virt_one(c, id)) return r;
+    return WSMC_OK;
+}
+
 static bool ew_reads_lagged(const wsmc_ctx* c, int32_t col) {
     for (int32_t x : c->ew_lag)
         if (x == col) return true;
@@ -2162,8 +2172,11 @@ int wsmc_assign(wsmc_ctx* c, int32_t out, const wsmc_operand* expr) {
     // column the batch reads through the ancestors -> launch it first
     if (b && b->nops > 0 &&
         (b->nops == kEwOps || (ind.mask && b->anc && b->anc != ind.row) || (out_read_behind && b->ntab == 4) ||
-         (!out_read_behind && ew_reads_lagged(c, out))))
-        if ((r = ew_flush(c))) return r;
+         (!out_read_behind && ew_reads_lagged(c, out)))) {
+        std::vector<int32_t> reads;
+        for (int k = 0; k < dim; ++k) cols_of(expr[k], reads);
+        if ((r = ew_flush_reads(c, reads))) return r;
+    }
     if (out_read_behind) {   // out read through the ancestors: write a fresh buffer (no read/write race)
         dst = c->cols[out].back;
         ind.tab_col = out;
@@ -2323,14 +2336,17 @@ int wsmc_sample(wsmc_ctx* c, int32_t out, const wsmc_dist* d) {
     if (ew_enabled(c)) {   // join the batch (its kernel writes the column in place)
         EwBatch* b = ew_open(c);
         if (b->nops > 0 && (b->nops == kEwOps || ew_reads_lagged(c, out)))
-            if ((r = ew_flush(c))) return r;
-        EwOp& eo = b->ops[b->nops];
-        std::memset(&eo, 0, sizeof(eo));
-        eo.s.d = *d;
-        auto stage = [&] { return ew_stage(c, b, [&] { return ew_remap_dist(c, b, eo.s.d); }); };
+            if ((r = ew_flush_reads(c, reads))) return r;
+        // the statement's slot: ops[nops], taken again after a launch (nops is then 0)
+        EwOp* eo = nullptr;
+        auto stage = [&] {
+            eo = &b->ops[b->nops];
+            std::memset(eo, 0, sizeof(*eo));
+            eo->s.d = *d;
+            return ew_stage(c, b, [&] { return ew_remap_dist(c, b, eo->s.d); });
+        };
         if (!stage()) {   // no room, or a column written without rows: launch the batch first
-            if ((r = ew_flush(c))) return r;
-            eo.s.d = *d;
+            if ((r = ew_flush_reads(c, reads))) return r;
             queued = stage();
         } else {
             queued = true;
@@ -2441,21 +2457,22 @@ static int weigh(wsmc_ctx* c, const wsmc_dist* d, const wsmc_operand* x, int kin
     if (ew_enabled(c)) {   // join the batch: its weight terms share one register and one max
         EwBatch* b = ew_open(c);
         if (b->nops == kEwOps)
-            if ((r = ew_flush(c))) return r;
-        EwOp& eo = b->ops[b->nops];
-        std::memset(&eo, 0, sizeof(eo));
-        eo.w.t = t;
+            if ((r = ew_flush_reads(c, reads))) return r;
+        // the statement's slot: ops[nops], taken again after a launch (nops is then 0)
+        EwOp* eo = nullptr;
         auto stage = [&] {
+            eo = &b->ops[b->nops];
+            std::memset(eo, 0, sizeof(*eo));
+            eo->w.t = t;
             return ew_stage(c, b, [&] {
-                if (!ew_remap_dist(c, b, eo.w.t.dist)) return false;
+                if (!ew_remap_dist(c, b, eo->w.t.dist)) return false;
                 for (int k = 0; k < 4; ++k)
-                    if (!ew_remap(c, b, eo.w.t.x[k])) return false;
+                    if (!ew_remap(c, b, eo->w.t.x[k])) return false;
                 return true;
             });
         };
         if (!stage()) {   // no room, or a column written without rows: launch the batch first
-            if ((r = ew_flush(c))) return r;
-            eo.w.t = t;
+            if ((r = ew_flush_reads(c, reads))) return r;
             queued = stage();
         } else {
             queued = true;
@@ -2557,7 +2574,8 @@ int wsmc_resample(wsmc_ctx* c, double ess_min, int32_t scheme, int32_t* resample
     }
     bool qs_done = false;
     if (fused_rs && c->ew && c->ew->nops > 0 && c->ew->has_w && c->ew_qs_ok && c->rs_qs && run_qstat_mode(c->N) != 0 &&
-        !(c->ew_feat & WSMC_FEAT_GAM) &&   // the statistics' form is two particles a thread (wsmc_jit.hip)
+        // the statistics' form is two particles a thread (wsmc_jit.hip ew_single)
+        !(c->ew_feat & (WSMC_FEAT_GAM | WSMC_FEAT_EXT)) &&
         ew_pair_ok(*c->ew, c->N)) {
         if (!c->run_nfix) {
             WSMC_HIP(hipMalloc(&c->run_nfix, sizeof(unsigned long long)));

@@ -193,8 +193,17 @@ bool ew_tables_lds(const EwSig& g) {
 // a batch with a log-Gamma family runs one particle a thread: two bounded rejection loops
 // unrolled side by side in a lane run one after the other anyway, put the pair's rows in scratch
 // (632 B a lane for a Binomial Sample + Observe) and, for a NegativeBinomial pair, took the
-// compiler down in its post-RA scheduler, which under hiprtc takes the process down with it
-bool ew_single(unsigned feat) { return (feat & WSMC_FEAT_GAM) != 0; }
+// compiler down in its post-RA scheduler, which under hiprtc takes the process down with it.
+// The same crash (ScheduleDAGInstrs::addVRegUseDeps under the PostRA Machine Instruction Scheduler
+// of the two-particle kernel) takes batches that hold a weight term and a family of
+// WSMC_FAM_EXPONENTIAL .. WSMC_FAM_RAYLEIGH (38 batch signatures of tests/progfuzz.py's programs;
+// tests/test_gpu_random_programs.py DIRECTED["ext_pair_compile"] is the shortest). The feature bits
+// are all a batch's kernel choice has, and WSMC_FEAT_EXT covers WSMC_FAM_BERNOULLI ..
+// WSMC_FAM_GEOMETRIC: every batch with one of those ten families (Bernoulli and Geometric too, which
+// were never seen to crash) now runs one particle a thread at even N and leaves the Resample
+// statistics to their own kernel (wsmc_resample). What that costs those batches has not been
+// measured; the benchmark's workload holds none of these families.
+bool ew_single(unsigned feat) { return (feat & (WSMC_FEAT_GAM | WSMC_FEAT_EXT)) != 0; }
 std::string tu_source(const std::string& sig, bool lds, bool qs, bool single) {
     const std::string head = std::string(lds ? "#define WSMC_TABLES_LDS 1\n" : "") + "#include \"wsmc_ew_body.h\"\n"
                              "struct WsmcSig { static constexpr wsmc::EwSig sig = " + sig + "; };\n";
