@@ -492,6 +492,16 @@ int wsmc_debug_mv_jit_selfcheck(void);
  * stats_out[3] = the generic Resamples whose statistics the statement batch took (round 6; its
  * misses, recomputed by k_rs_qfix, count in stats_out[0]). stats_out holds 4 values. */
 int wsmc_debug_run_stats(wsmc_ctx* ctx, int64_t* stats_out);
+/* The fused 2D-SSM run's weight rows, counted on the device by the
+ * propagate launches themselves and cumulative over the context's runs (a sharded handle reports
+ * its first shard): stats_out[0] = the launches with the Resample statistics (steps 2..T of a
+ * stratified or systematic run) that stored their weight row, stats_out[1] = those that recomputed
+ * the previous step's row instead of loading it, stats_out[2] = those launches in all,
+ * stats_out[3] = the launches without the statistics (step 1, the multinomial scheme, an exact
+ * replay), which always store. A one-GPU run in statistics mode 1 stores the row of step t >= 2
+ * only when step t - 1 did not resample or t is the last step; every other layout stores every
+ * row. stats_out holds 4 values. */
+int wsmc_debug_weight_stores(wsmc_ctx* ctx, int64_t* stats_out);
 
 #ifdef __cplusplus
 }

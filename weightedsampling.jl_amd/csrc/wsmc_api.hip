@@ -777,7 +777,7 @@ int wsmc_destroy(wsmc_ctx* c) {
     }
     for (void* p : c->row_slabs) (void)hipFree(p);   // every row (log, pool, eager, anc_keep) lives in a slab
     void* bufs[] = {c->dec_always, c->xchg, c->scache, c->scache_back, c->w, c->anc, c->tmp, c->tilep, c->tileOff, c->taskOff, c->taskTile, c->mslots, c->qbuf, c->cdf, c->tilepart, c->rec, c->dec, c->mom, c->dflag, c->ucount, c->wslots[0], c->wslots[1],
-                    c->d_colptr, c->run_params, c->d_tape, c->run_max, c->run_rec, c->run_dec, c->anc_log, c->obs_buf, c->run_grp, c->run_rg, c->run_nfix, c->run_w0,
+                    c->d_colptr, c->run_params, c->d_tape, c->run_max, c->run_rec, c->run_dec, c->anc_log, c->obs_buf, c->run_grp, c->run_rg, c->run_nfix, c->run_wcnt, c->run_w0,
                     c->vscratch, c->xscratch, c->xp, c->comb, c->anc_out, c->xbuf, c->d_comp, c->d_ctape, c->d_prog, c->rs_grp[0], c->rs_grp[1], c->rs_qs,
                     c->xpairs, c->xnb, c->xwin, c->xstat, c->w_save, c->xms, c->xanc, c->xlines, c->xpeer,
                     c->lg_data, c->lg_trace, c->lg_rec};
@@ -3782,6 +3782,10 @@ static int ensure_run_buffers(wsmc_ctx* c, int32_t T) {
         WSMC_HIP(hipMalloc(&c->run_nfix, sizeof(unsigned long long)));
         WSMC_HIP(hipMemsetAsync(c->run_nfix, 0, sizeof(unsigned long long), c->stream));
     }
+    if (!c->run_wcnt) {
+        WSMC_HIP(hipMalloc(&c->run_wcnt, sizeof(unsigned long long) * 4));
+        WSMC_HIP(hipMemsetAsync(c->run_wcnt, 0, sizeof(unsigned long long) * 4, c->stream));
+    }
     WSMC_HIP(hipMalloc(&c->run_rec, sizeof(ShardRecord) * (T + 1) * kMaxWorld));
     WSMC_HIP(hipMalloc(&c->run_dec, sizeof(Decision) * (T + 1)));
     WSMC_HIP(hipMalloc(&c->anc_log, sizeof(int32_t) * (size_t)T * anc_stride(c->N)));
@@ -3944,7 +3948,13 @@ static int enqueue_ssm2d(wsmc_ctx* c, const RunPlan& p, const std::vector<hipEve
             a.grp = c->run_grp + (size_t)t * run_grp_words(N);
             a.G = G;
             a.qbuf = qs == 1 ? c->qbuf : nullptr;
+            // one GPU, q stored: only the next propagate (after a step that did not resample) and
+            // the trace-back (the last step's row) read a step's weights, so the row is stored for
+            // them alone (k_ssm2d_prop). Shards (k_rs_qfix), the fill of mode 2, the multinomial
+            // scheme and the exact replay read it themselves and keep every store.
+            if (!sharded && qs == 1) a.w_lazy = (t < T ? kWLazySkip : 0) | (t > 2 ? kWLazyPrev : 0);
         }
+        a.wcnt = c->run_wcnt;
         const int k0 = 8 * (t - 1);
         WSMC_HIP(launch_ssm2d_propagate(c->stream, a, E(k0), E(k0 + 1)));
         const FillPlan plan = fill_plan(c, p.scheme, 3ull * (uint64_t)(t - 1) + 2ull, c->run_op);
@@ -5285,6 +5295,18 @@ int wsmc_debug_run_stats(wsmc_ctx* c, int64_t* stats_out) {
     stats_out[1] = run_qstat_mode(c->N);
     stats_out[2] = c->run_replays;
     stats_out[3] = c->rs_qs_batches;
+    return WSMC_OK;
+}
+
+int wsmc_debug_weight_stores(wsmc_ctx* c, int64_t* stats_out) {
+    if (c && c->multi) return wsmc_debug_weight_stores(multi_first(c), stats_out);
+    if (!c || !stats_out) return fail(WSMC_EARG, "null argument");
+    unsigned long long n[4] = {0, 0, 0, 0};
+    if (c->run_wcnt) {   // counted by the propagates themselves (k_ssm2d_prop, block 0)
+        WSMC_HIP(ctx_sync(c, c->stream));
+        WSMC_HIP(hipMemcpy(n, c->run_wcnt, sizeof(n), hipMemcpyDeviceToHost));
+    }
+    for (int k = 0; k < 4; ++k) stats_out[k] = (int64_t)n[k];
     return WSMC_OK;
 }
 

@@ -346,6 +346,7 @@ struct wsmc_ctx {
     wsmc::MaxSlots* run_max = nullptr;      // [T+1]
     double* run_rg = nullptr;               // [T+1] the propagate's guessed reference points (round 6)
     unsigned long long* run_nfix = nullptr; // [1] steps whose statistics k_rs_qfix recomputed (cumulative)
+    unsigned long long* run_wcnt = nullptr; // [4] the propagates' weight-row counts (Ssm2dArgs::wcnt, cumulative)
     double* run_w0 = nullptr;               // [2][N] the weights a run started from (its replay's start), by parity
     // asynchronous fused runs (round 6): wsmc_ssm2d_run returns once its graph is launched; the
     // decisions come back into pinned memory behind it and the next entry point (or the next run,
@@ -814,7 +815,16 @@ struct Ssm2dArgs {
     unsigned long long* grp = nullptr;
     int32_t G = 1;
     unsigned long long* qbuf = nullptr;
+    // lazy weight rows (round 9; one-GPU runs in statistics mode 1, where only a propagate reads a
+    // step's weights): kWLazySkip = do not store this step's row when the previous step resampled
+    // (set at t < T), kWLazyPrev = the previous step may have skipped its store (set at t > 2):
+    // after a step that did not resample, itself after one that did, recompute its row
+    int32_t w_lazy = 0;
+    // [4] cumulative, or null: launches with the statistics that stored the row / that recomputed
+    // the previous row / in all, launches without the statistics (wsmc_debug_weight_stores)
+    unsigned long long* wcnt = nullptr;
 };
+constexpr int32_t kWLazySkip = 1, kWLazyPrev = 2;
 // k_rs_qfix: the statistics again against ceil(M) when the propagate's guess was not it
 hipError_t launch_rs_qfix(hipStream_t s, const double* w, int64_t N, const MaxSlots* ms, const double* rg,
                           unsigned long long* tilep, unsigned long long* qbuf, unsigned long long* grp, int G,

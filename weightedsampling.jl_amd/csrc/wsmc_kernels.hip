@@ -3294,6 +3294,18 @@ __device__ __forceinline__ double aff2(double a, double b) {
     return v;
 }
 
+// o => MvNormal(x, r*I): the observation's log-density at one particle. One source expression for
+// the step that adds it to the weight and for a later step that recomputes that weight from the
+// stored x (Ssm2dArgs::w_lazy): the same IEEE operations, so the same bits.
+__device__ __forceinline__ double ssm2d_obs_lp(double x0, double x1, double o0, double o1, double c0, double r_var) {
+    const double m0 = 0.0 + 1.0 * x0, m1 = 0.0 + 1.0 * x1;
+    double s = 0.0;
+    const double d0 = o0 - m0, d1 = o1 - m1;
+    s = s + d0 * d0;
+    s = s + d1 * d1;
+    return -(c0 + s / r_var) * 0.5;
+}
+
 // One step of the fused 2D SSM (examples/2D_ssm.jl:11-16) for two adjacent particles per
 // thread. The run's working state is particle-major pairs ([N][2]: x_t, v, dv), so each
 // gather through an ancestor is one 16-B load and every store (x, v, w pairs) is 16 B per
@@ -3330,6 +3342,14 @@ __device__ __forceinline__ double aff2(double a, double b) {
 // under that first round trip, the rest after the gathers are issued, and every gather is a load
 // under no branch, so no wait that covers a gather precedes the last draw instruction
 // (tests/test_kernel_isa.py reads that order from the saved assembly).
+// QS, one GPU (round 9, Ssm2dArgs::w_lazy): the weight pair is stored only when a step will read
+// it. Nothing reads step t's row when step t-1 resampled and t < T (the next propagate starts from
+// the log-mean, the fill reads q), so kWLazySkip drops the store then. A step that follows a step
+// which did not resample, itself after one that did, finds no stored row (kWLazyPrev) and
+// recomputes it: w_{t-1}[i] = dec[t-2].mean + lp(x_t[i], obs_{t-1}), the x it loads anyway (src =
+// i) through ssm2d_obs_lp, the same operations as the step that skipped the store. Both choices
+// are the same for the whole grid. Block 0 counts the launch, its store and its recompute into
+// wcnt (wsmc_debug_weight_stores).
 template <int MODE, int IT = 1, int NT = kBlock, bool QS = false, bool ISL = false>
 __global__ __launch_bounds__(NT) void k_ssm2d_prop(Ssm2dArgs a) {
     WSMC_BLK_CLOCK(QS ? 0 : 3);
@@ -3498,7 +3518,36 @@ __global__ __launch_bounds__(NT) void k_ssm2d_prop(Ssm2dArgs a) {
         const double lpmax = -(ARG_LATE(c0) + 0.0) * 0.5;
         Rg = wsmc_qref(base + lpmax);
         sK = wsmc_pow2i(wsmc_qbits((uint64_t)N));
-        if (blockIdx.x == 0 && threadIdx.x == 0) *ARG_LATE(rg_out) = Rg;
+    }
+    // the lazy weight rows: read late, from the argument segment and inside the `!rs` branch, so
+    // none of it is live beside the Philox key schedule
+    bool wstore = true, wrecomp = false;
+    double wmean2 = 0.0, po0 = 0.0, po1 = 0.0;
+    if (QS && !ISL) {
+        const int32_t lazy = ARG_LATE(w_lazy);
+        wstore = !(lazy & kWLazySkip) || !rs;
+        if (!rs && (lazy & kWLazyPrev)) {
+            // step t-2's decision and step t-1's observation, both written by earlier launches:
+            // read as constants, that is by scalar loads, which no wait for the gathers covers
+            typedef const Decision __attribute__((address_space(4)))* DecK;
+            typedef const double __attribute__((address_space(4)))* ObsK;
+            const DecK dec2 = (DecK)(ARG_LATE(dec_prev) - 1);
+            if (dec2->resampled) {   // step t-1 skipped its store: its weights again, from x_t
+                const ObsK pobs = (ObsK)(ARG_LATE(obs) + 2 * (ARG_LATE(t) - 2));
+                wrecomp = true;
+                wmean2 = dec2->mean;
+                po0 = pobs[0];
+                po1 = pobs[1];
+            }
+        }
+    }
+    if (QS && blockIdx.x == 0 && threadIdx.x == 0) {
+        *ARG_LATE(rg_out) = Rg;
+        if (unsigned long long* const wc = ARG_LATE(wcnt)) {   // no result read back: off every chain
+            atomicAdd(wc + 2, 1ull);
+            if (wstore) atomicAdd(wc, 1ull);
+            if (wrecomp) atomicAdd(wc + 1, 1ull);
+        }
     }
     double zs[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
     if (kSplitDraw) {   // the draws' second part, with the gathers in flight
@@ -3533,13 +3582,10 @@ __global__ __launch_bounds__(NT) void k_ssm2d_prop(Ssm2dArgs a) {
             // v .= v + dv
             const double vn0 = aff2(vp[j][k].x, dv0), vn1 = aff2(vp[j][k].y, dv1);
             // o => MvNormal(x{t+1}, r*I)
-            const double m0 = 0.0 + 1.0 * xn0, m1 = 0.0 + 1.0 * xn1;
-            double s = 0.0;
-            const double d0 = o0 - m0, d1 = o1 - m1;
-            s = s + d0 * d0;
-            s = s + d1 * d1;
-            const double lp = -(ARG_LATE(c0) + s / ARG_LATE(r_var)) * 0.5;
-            wn[k] = wb[j][k] + lp;
+            const double lp = ssm2d_obs_lp(xn0, xn1, o0, o1, ARG_LATE(c0), ARG_LATE(r_var));
+            double wbk = wb[j][k];
+            if (wrecomp) wbk = wmean2 + ssm2d_obs_lp(xp[j][k].x, xp[j][k].y, po0, po1, ARG_LATE(c0), ARG_LATE(r_var));
+            wn[k] = wbk + lp;
             xn[k] = d2{xn0, xn1};
             vn[k] = d2{vn0, vn1};
             dvv[k] = d2{dv0, dv1};
@@ -3555,13 +3601,13 @@ __global__ __launch_bounds__(NT) void k_ssm2d_prop(Ssm2dArgs a) {
             *reinterpret_cast<d2*>(ARG_LATE(x_next) + 2 * i0 + 2) = xn[1];
             *reinterpret_cast<d2*>(ARG_LATE(v_next) + 2 * i0 + 2) = vn[1];
             if (ARG_LATE(dv)) *reinterpret_cast<d2*>(ARG_LATE(dv) + 2 * i0 + 2) = dvv[1];
-            *reinterpret_cast<d2*>(ARG_LATE(w) + i0) = d2{wn[0], wn[1]};
+            if (wstore) *reinterpret_cast<d2*>(ARG_LATE(w) + i0) = d2{wn[0], wn[1]};
             const u64 e1 = wsmc_ord_enc(wn[1]);
             menc = e1 > menc ? e1 : menc;
             if (QS) q1 = qacc_add(acc, wsmc_expw(wn[1] - Rg), sK);
             if (QS && ARG_LATE(qbuf)) *reinterpret_cast<ulonglong2*>(ARG_LATE(qbuf) + i0) = make_ulonglong2(q0, q1);
         } else {
-            ARG_LATE(w)[i0] = wn[0];
+            if (wstore) ARG_LATE(w)[i0] = wn[0];
             if (QS && ARG_LATE(qbuf)) ARG_LATE(qbuf)[i0] = q0;
         }
     }
@@ -3595,6 +3641,8 @@ __global__ __launch_bounds__(NT) void k_ssm2d_prop(Ssm2dArgs a) {
         }
         return;
     }
+    // (a launch without the statistics always stores its row)
+    if (a.wcnt && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(a.wcnt + 3, 1ull);
     if (MODE & 4) {                                  // diag: no block max / atomic
         if (menc == 0x123456789ull) ARG_LATE(w)[0] = 0.0;
         return;

@@ -406,6 +406,15 @@ class Context:
         check(self._L.wsmc_debug_run_stats(self._h, st))
         return {"missed_steps": st[0], "qstat_mode": st[1], "replays": st[2], "batch_statistics": st[3]}
 
+    def weight_stores(self) -> dict:
+        """The fused run's weight rows, counted by the propagate launches on the device
+        (wsmc_debug_weight_stores, cumulative): the launches with the Resample statistics that
+        stored their row, that recomputed the previous row, their number, and the launches without
+        the statistics (which always store)."""
+        st = (C.c_int64 * 4)()
+        check(self._L.wsmc_debug_weight_stores(self._h, st))
+        return {"stored": st[0], "recomputed": st[1], "qs_launches": st[2], "plain_launches": st[3]}
+
     def ssm2d_run(self, obs, x0=(0.0, 0.0), v0=(1.0, 0.0), q_var=0.1, r_var=0.5, ess_perc_min=0.5,
                   scheme: int = abi.RESAMPLE_STRATIFIED, keep_history: bool = True,
                   want_evidence: bool = True):
