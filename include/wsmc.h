@@ -430,6 +430,82 @@ int wsmc_lgssm1d_run(wsmc_ctx* ctx, const double* data, int32_t T, double a, dou
  * the statement route, segments launched (cumulative per context), then the last run's host
  * bookkeeping time (tape and state, done while the device runs) and whole-call time, microseconds. */
 int wsmc_debug_lgssm(wsmc_ctx* ctx, int32_t segment_steps, int64_t* stats_out);
+/* ---- a scalar state-space model the caller specifies, as one call ----------------------
+ * The step body wsmc_lgssm1d_run hard-codes, described instead: up to WSMC_SSM_MAX_COLS scalar
+ * (dim-1) state columns, an `init` list run once at the start of the call and a `step` list run
+ * for t = 0 .. T-1. Operands, dists and programs inside a spec name the spec's columns by their
+ * local index 0 .. n_cols-1; the run creates the columns that are missing (in order) and maps
+ * the indices to column ids.
+ *   SAMPLE       col ~ dist                      (wsmc_sample)
+ *   ASSIGN       col .= value                    (wsmc_assign)
+ *   ASSIGN_EXPR  col .= prog[0 .. prog_len)      (wsmc_assign_expr: one postfix program of at
+ *                                                 most WSMC_SSM_XPROG_MAX instructions)
+ *   OBSERVE      value => dist                   (wsmc_observe)
+ * A Resample(ess_perc_min, scheme) follows every SAMPLE and every OBSERVE (what @model inserts);
+ * it takes its op counter whether or not it runs, and runs only if the weights changed.
+ * dists: dim 1, WSMC_MEAN_AFFINE, family NORMAL, HALFNORMAL, UNIFORM, 5 .. 14 or 16 .. 23.
+ * Data: the call takes a row-major T x data_dim table (data_dim <= WSMC_SSM_MAX_DATA). In an
+ * operand of `step` at most one slot k may have col[k] == WSMC_OPERAND_DATA with comp[k] = j <
+ * data_dim: the operand's value at step t is that of the same operand with slot k removed and
+ * c0 = data[t][j] (it must have c0 == 0 and coef[k] == 1, so the fold is exact: the constant
+ * operand the statements get). In a program WSMC_X_COL with col == WSMC_OPERAND_DATA pushes
+ * data[t][comp]. `init` reads no data; `step` holds at least one OBSERVE. */
+#define WSMC_SSM_MAX_COLS 4
+#define WSMC_SSM_MAX_INIT 4
+#define WSMC_SSM_MAX_STMTS 8
+#define WSMC_SSM_MAX_DATA 4
+#define WSMC_SSM_XPROG_MAX 32
+#define WSMC_SSM_NAME_MAX 32
+#define WSMC_OPERAND_DATA (-2)
+typedef enum {
+    WSMC_SSM_SAMPLE = 0, WSMC_SSM_ASSIGN = 1, WSMC_SSM_ASSIGN_EXPR = 2, WSMC_SSM_OBSERVE = 3
+} wsmc_ssm_kind;
+typedef struct {
+    int32_t kind;               /* wsmc_ssm_kind */
+    int32_t col;                /* SAMPLE, ASSIGN, ASSIGN_EXPR: the output column (local index) */
+    int32_t prog_len;           /* ASSIGN_EXPR: instructions of prog */
+    int32_t reserved;
+    wsmc_dist dist;             /* SAMPLE, OBSERVE */
+    wsmc_operand value;         /* ASSIGN: the right-hand side; OBSERVE: the observed value */
+    wsmc_xinst prog[WSMC_SSM_XPROG_MAX];
+} wsmc_ssm_stmt;
+typedef struct {
+    int32_t n_cols;             /* 1 .. WSMC_SSM_MAX_COLS */
+    int32_t data_dim;           /* 0 .. WSMC_SSM_MAX_DATA columns of the data table */
+    int32_t n_init;             /* 0 .. WSMC_SSM_MAX_INIT */
+    int32_t n_step;             /* 1 .. WSMC_SSM_MAX_STMTS */
+    char col_names[WSMC_SSM_MAX_COLS][WSMC_SSM_NAME_MAX];   /* NUL-terminated, distinct */
+    wsmc_ssm_stmt init[WSMC_SSM_MAX_INIT];
+    wsmc_ssm_stmt step[WSMC_SSM_MAX_STMTS];
+} wsmc_ssm_spec;
+/* The rules above, on the host alone (no device call, no context): WSMC_OK, or WSMC_EARG with
+ * the reason in wsmc_last_error(). */
+int wsmc_ssm_spec_check(const wsmc_ssm_spec* spec);
+/* sizeof(wsmc_ssm_stmt) and sizeof(wsmc_ssm_spec) as the library was built (layout checks) */
+int wsmc_ssm_spec_sizeof(int64_t* stmt_bytes, int64_t* spec_bytes);
+/* Runs the spec: on return the columns, weights, ancestors, every wsmc_state field, the score
+ * tape, the evidence and the RNG stream positions are, bit for bit, those of issuing the spec's
+ * statements (and their Resamples) one by one through the operators above, with the step's data
+ * folded into constants. Synchronous: on return the run is complete and folded in.
+ * One unsharded context that holds no column but the spec's (dim 1), with at most
+ * wsmc_debug_ssm's cap particles for the spec's column count, weights_changed clear, a
+ * stratified or systematic scheme and at most WSMC_XPROG_MAX program instructions in the whole
+ * spec runs on one persistent workgroup (the columns in LDS, the steps looped on the device, a
+ * launch per segment of steps); everything else issues the statements themselves inside the
+ * library, which is also the definition of the results.
+ * data: T x spec->data_dim, row-major (may be NULL when data_dim == 0).
+ * ess_trace_out (may be NULL): T doubles, the ESS% computed by the Resample that follows each
+ * step's last OBSERVE (NaN kept).
+ * WSMC_EARG: a spec wsmc_ssm_spec_check refuses, T < 1, null data, an unknown scheme, a spec
+ * column that exists with another dimension. */
+int wsmc_ssm_run(wsmc_ctx* ctx, const wsmc_ssm_spec* spec, const double* data, int32_t T,
+                 double ess_perc_min, int32_t scheme, double* log_evidence_out, double* ess_trace_out);
+/* segment_steps > 0 sets the steps per launch, 0 restores the default, < 0 leaves it; stats_out[9]
+ * (may be NULL) = the largest N the persistent kernel takes with 1, 2, 3, 4 columns, the runs it
+ * took, the runs that went through the statement route, the segments launched (cumulative per
+ * context), then the last run's host bookkeeping time (tape and state, done while the device
+ * runs) and whole-call time, microseconds. */
+int wsmc_debug_ssm(wsmc_ctx* ctx, int32_t segment_steps, int64_t* stats_out);
 /* per-kernel timing of the last fused run (HIP events on the ctx stream), ms */
 typedef struct {
     double total_ms;            /* whole run, first kernel to last                       */

@@ -1,0 +1,155 @@
+"""The fused run of a specified scalar SSM (wsmc_ssm_run) against the statement route of the same
+tree, at N = 1000 with forced resampling: the four models of wsmc.models.SSM_MODELS, and the LGSSM
+spec on the generic kernel against wsmc_lgssm1d_run on the hard-coded one.
+
+    python tools/bench_ssm.py                  every model at T = 1e3, 1e4, 1e5 (the driver)
+    python tools/bench_ssm.py --leg sv --T 10000    one measurement in this process (one JSON line)
+
+The driver starts one child process per (model, T), each under its own `timeout`: the T = 1e3 run
+comes first and sizes the limits of the longer ones. A child that fails, or runs into its limit,
+ends the driver: nothing more is started on the device. Each child times, in one process, after a
+warm-up run, the best of 2:
+
+  persistent     Context.ssm_run (the persistent workgroup)
+  statements     spec.statements on a Context, the Resamples asynchronous (the Python loop over
+                 the operators: what a user's own loop costs)
+  statements_lib Context.ssm_run with a foreign column present, which sends the same spec through
+                 the statement loop inside the library (no Python between the statements)
+  lgssm leg only lgssm1d_run (k_lgssm_segment) beside ssm_run of the LGSSM spec (k_ssm_segment)
+
+One JSON line per child, appended to profiles/ssm_fused.jsonl. Diagnostics for DESIGN.md §4;
+bench.py stays the headline."""
+import argparse
+import json
+import pathlib
+import subprocess
+import sys
+import time
+
+ROOT = pathlib.Path(__file__).resolve().parents[1]
+sys.path[:0] = [str(ROOT / "weightedsampling.jl_amd"), str(ROOT / "oracle"), str(ROOT)]
+
+N = 1000
+LEGS = ["sv", "poisson_count", "kitagawa", "local_trend", "lgssm"]
+OUT = ROOT / "profiles" / "ssm_fused.jsonl"
+
+
+def best_of(run, reps=2):
+    """run() -> (seconds, extra) on a fresh context; a warm-up first, then the best of `reps`"""
+    best, extra = float("inf"), None
+    for k in range(reps + 1):
+        dt, ex = run()
+        if k > 0 and dt < best:
+            best, extra = dt, ex
+    return best, extra
+
+
+def child(leg: str, T: int) -> dict:
+    import wsmc
+    from wsmc import models
+    if leg == "lgssm":
+        spec, data = models.lgssm1d_spec(), models.lgssm1d_data(T)
+    else:
+        make, gen = models.SSM_MODELS[leg]
+        spec, data = make(), gen(T)
+    spec.check()
+
+    def persistent():
+        ctx = wsmc.Context(N, seed=42)
+        ctx.sync()
+        t0 = time.perf_counter()
+        ctx.ssm_run(spec, data, ess_perc_min=1.0, want_evidence=False)
+        dt = time.perf_counter() - t0
+        st = ctx.ssm_stats()
+        assert st["persistent_runs"] == 1, st
+        ex = {"log_evidence": ctx.log_evidence(), "resamples": ctx.get_state()["n_resamples"],
+              "host_bookkeeping_s": st["bookkeeping_s"], "segments": st["segments"]}
+        ctx.close()
+        return dt, ex
+
+    def statements():
+        ctx = wsmc.Context(N, seed=42)
+        ctx.sync()
+        t0 = time.perf_counter()
+        spec.statements(ctx, data, ess_perc_min=1.0, wait=False)
+        ctx.sync()
+        dt = time.perf_counter() - t0
+        ex = {"log_evidence": ctx.log_evidence(), "resamples": ctx.get_state()["n_resamples"]}
+        ctx.close()
+        return dt, ex
+
+    def statements_lib():
+        ctx = wsmc.Context(N, seed=42)
+        ctx.assign(ctx.col_create("_other", 1), models._const([0.0]))   # a foreign column: the statement route
+        ctx.sync()
+        t0 = time.perf_counter()
+        ctx.ssm_run(spec, data, ess_perc_min=1.0, want_evidence=False)
+        dt = time.perf_counter() - t0
+        assert ctx.ssm_stats()["statement_runs"] == 1
+        ex = {"log_evidence": ctx.log_evidence(), "resamples": ctx.get_state()["n_resamples"]}
+        ctx.close()
+        return dt, ex
+
+    def lgssm_kernel():
+        ctx = wsmc.Context(N, seed=42)
+        ctx.sync()
+        t0 = time.perf_counter()
+        ctx.lgssm1d_run(data, ess_perc_min=1.0, want_evidence=False)
+        dt = time.perf_counter() - t0
+        assert ctx.lgssm_stats()["persistent_runs"] == 1
+        ex = {"log_evidence": ctx.log_evidence(), "resamples": ctx.get_state()["n_resamples"]}
+        ctx.close()
+        return dt, ex
+
+    p, pe = best_of(persistent)
+    s, se = best_of(statements)
+    sl, sle = best_of(statements_lib)
+    # the three routes compute the same thing
+    assert pe["log_evidence"] == se["log_evidence"] == sle["log_evidence"], (pe, se, sle)
+    assert pe["resamples"] == se["resamples"] == sle["resamples"] == T
+    out = {"leg": leg, "N": N, "T": T, "columns": len(spec.cols), "step_statements": spec.spec.n_step,
+           "persistent_s": p, "persistent_us_per_step": 1e6 * p / T,
+           "statements_s": s, "statements_us_per_step": 1e6 * s / T,
+           "statements_lib_s": sl, "statements_lib_us_per_step": 1e6 * sl / T,
+           "factor_vs_statements": s / p, "factor_vs_statements_lib": sl / p,
+           "host_bookkeeping_s": pe["host_bookkeeping_s"], "segments": pe["segments"],
+           "log_evidence": pe["log_evidence"]}
+    if leg == "lgssm":
+        k, ke = best_of(lgssm_kernel)
+        assert ke["log_evidence"] == pe["log_evidence"]
+        out.update(lgssm1d_run_s=k, lgssm1d_run_us_per_step=1e6 * k / T, generic_over_hard_coded=p / k)
+    return out
+
+
+def driver(Ts, legs) -> int:
+    OUT.parent.mkdir(exist_ok=True)
+    for leg in legs:
+        per_step = None   # seconds a step of one child (all its routes and repetitions), from the run before
+        for T in Ts:
+            limit = 180 if per_step is None else int(60 + 3 * per_step * T)
+            cmd = ["timeout", "-k", "10", str(limit), sys.executable, __file__, "--leg", leg, "--T", str(T)]
+            t0 = time.perf_counter()
+            r = subprocess.run(cmd, capture_output=True, text=True)
+            dt = time.perf_counter() - t0
+            if r.returncode != 0:
+                print(f"{leg} T={T}: exit {r.returncode} (limit {limit} s)\n{r.stdout}\n{r.stderr}", flush=True)
+                return 1   # nothing more is started on the device
+            line = r.stdout.strip().splitlines()[-1]
+            json.loads(line)
+            with open(OUT, "a") as f:
+                f.write(line + "\n")
+            print(line, flush=True)
+            per_step = dt / T
+    return 0
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--leg", choices=LEGS)
+    ap.add_argument("--T", type=int, action="append")
+    ap.add_argument("--legs", default=",".join(LEGS))
+    a = ap.parse_args()
+    if a.leg:
+        print(json.dumps(child(a.leg, (a.T or [1000])[0])), flush=True)
+        sys.exit(0)
+    sys.exit(driver(a.T or [1000, 10_000, 100_000], a.legs.split(",")))

@@ -5275,6 +5275,397 @@ int wsmc_debug_lgssm(wsmc_ctx* c, int32_t segment_steps, int64_t* stats_out) {
     return WSMC_OK;
 }
 
+// ---- fused run of a caller-specified scalar SSM (csrc/wsmc_ssm.hip) -----------------------------
+static bool ssm_family_ok(int32_t f) {
+    return f == WSMC_FAM_NORMAL || f == WSMC_FAM_HALFNORMAL || f == WSMC_FAM_UNIFORM ||
+           (f >= WSMC_FAM_BERNOULLI && f <= WSMC_FAM_GEOMETRIC) || (f >= WSMC_FAM_GAMMA && f <= WSMC_FAM_NEGBINOMIAL);
+}
+// why the spec refuses the operand, or null
+static const char* ssm_operand_why(const wsmc_ssm_spec* sp, const wsmc_operand& o, bool step) {
+    int ndata = 0;
+    for (int k = 0; k < 2; ++k) {
+        const int32_t col = o.col[k];
+        if (col == WSMC_OPERAND_DATA) {
+            if (!step) return "init reads data";
+            if (o.comp[k] < 0 || o.comp[k] >= sp->data_dim) return "a data reference past data_dim";
+            if (!(o.coef[k] == 1.0)) return "a data reference needs coef == 1";
+            ndata += 1;
+        } else if (col >= 0) {
+            if (col >= sp->n_cols) return "a column index past n_cols";
+            if (o.comp[k] != 0) return "a component other than 0 of a scalar column";
+        }
+    }
+    if (ndata > 1) return "two data slots in one operand";
+    if (ndata == 1 && !(o.c0 == 0.0)) return "a data reference needs c0 == 0";
+    return nullptr;
+}
+static const char* ssm_stmt_why(const wsmc_ssm_spec* sp, const wsmc_ssm_stmt& s, bool step) {
+    const bool dist = s.kind == WSMC_SSM_SAMPLE || s.kind == WSMC_SSM_OBSERVE;
+    if (!dist && s.kind != WSMC_SSM_ASSIGN && s.kind != WSMC_SSM_ASSIGN_EXPR) return "an unknown statement kind";
+    if (s.kind != WSMC_SSM_OBSERVE && (s.col < 0 || s.col >= sp->n_cols)) return "an output column index past n_cols";
+    if (dist) {
+        const wsmc_dist& d = s.dist;
+        if (!ssm_family_ok(d.family)) return "a family that is not a scalar one (or unknown)";
+        if (d.dim != 1) return "a dist of dim != 1";
+        if (d.mean_fn != WSMC_MEAN_AFFINE) return "a mean function other than WSMC_MEAN_AFFINE";
+        for (int k = 0; k < 4; ++k)
+            if (const char* w = ssm_operand_why(sp, d.mu[k], step)) return w;
+        if (const char* w = ssm_operand_why(sp, d.scale, step)) return w;
+    }
+    if (s.kind == WSMC_SSM_ASSIGN || s.kind == WSMC_SSM_OBSERVE)
+        if (const char* w = ssm_operand_why(sp, s.value, step)) return w;
+    if (s.kind == WSMC_SSM_ASSIGN_EXPR) {
+        if (s.prog_len < 1 || s.prog_len > WSMC_SSM_XPROG_MAX) return "a program of less than 1 or more than WSMC_SSM_XPROG_MAX instructions";
+        const int32_t len[1] = {s.prog_len};
+        if (wsmc_xprog_check(s.prog, len, 1)) return "a malformed program (wsmc_xprog_check)";
+        for (int q = 0; q < s.prog_len; ++q) {
+            if (s.prog[q].op != WSMC_X_COL) continue;
+            if (s.prog[q].col == WSMC_OPERAND_DATA) {
+                if (!step) return "init reads data";
+                if (s.prog[q].comp < 0 || s.prog[q].comp >= sp->data_dim) return "a data reference past data_dim";
+            } else {
+                if (s.prog[q].col < 0 || s.prog[q].col >= sp->n_cols) return "a column index past n_cols";
+                if (s.prog[q].comp != 0) return "a component other than 0 of a scalar column";
+            }
+        }
+    }
+    return nullptr;
+}
+static const char* ssm_spec_why(const wsmc_ssm_spec* sp) {
+    if (!sp) return "null spec";
+    if (sp->n_cols < 1 || sp->n_cols > WSMC_SSM_MAX_COLS) return "n_cols must be 1..WSMC_SSM_MAX_COLS";
+    if (sp->data_dim < 0 || sp->data_dim > WSMC_SSM_MAX_DATA) return "data_dim must be 0..WSMC_SSM_MAX_DATA";
+    if (sp->n_init < 0 || sp->n_init > WSMC_SSM_MAX_INIT) return "n_init must be 0..WSMC_SSM_MAX_INIT";
+    if (sp->n_step < 1 || sp->n_step > WSMC_SSM_MAX_STMTS) return "n_step must be 1..WSMC_SSM_MAX_STMTS";
+    for (int k = 0; k < sp->n_cols; ++k) {
+        const char* n = sp->col_names[k];
+        if (!n[0] || !std::memchr(n, 0, WSMC_SSM_NAME_MAX)) return "a column name that is empty or not terminated";
+        for (int j = 0; j < k; ++j)
+            if (!std::strcmp(n, sp->col_names[j])) return "two columns of one name";
+    }
+    for (int q = 0; q < sp->n_init; ++q)
+        if (const char* w = ssm_stmt_why(sp, sp->init[q], false)) return w;
+    bool observes = false;
+    for (int q = 0; q < sp->n_step; ++q) {
+        if (const char* w = ssm_stmt_why(sp, sp->step[q], true)) return w;
+        observes |= sp->step[q].kind == WSMC_SSM_OBSERVE;
+    }
+    if (!observes) return "step holds no OBSERVE";
+    return nullptr;
+}
+
+int wsmc_ssm_spec_check(const wsmc_ssm_spec* spec) {
+    if (const char* w = ssm_spec_why(spec)) return fail(WSMC_EARG, std::string("ssm spec: ") + w);
+    return WSMC_OK;
+}
+
+int wsmc_ssm_spec_sizeof(int64_t* stmt_bytes, int64_t* spec_bytes) {
+    if (stmt_bytes) *stmt_bytes = (int64_t)sizeof(wsmc_ssm_stmt);
+    if (spec_bytes) *spec_bytes = (int64_t)sizeof(wsmc_ssm_spec);
+    return WSMC_OK;
+}
+
+// the operand as the statements get it: local indices to column ids, a data slot removed and the
+// step's value in c0 (row: the step's data row, null in `init`)
+static wsmc_operand ssm_map_operand(const wsmc_operand& o, const int32_t* ids, const double* row) {
+    wsmc_operand r = o;
+    for (int k = 0; k < 2; ++k) {
+        if (o.col[k] == WSMC_OPERAND_DATA) {
+            r.c0 = row[o.comp[k]];
+            r.col[k] = -1;
+            r.comp[k] = 0;
+            r.coef[k] = 0.0;
+        } else if (o.col[k] >= 0) {
+            r.col[k] = ids[o.col[k]];
+        }
+    }
+    return r;
+}
+static wsmc_dist ssm_map_dist(const wsmc_dist& d, const int32_t* ids, const double* row) {
+    wsmc_dist r = d;
+    for (int k = 0; k < 4; ++k) r.mu[k] = ssm_map_operand(d.mu[k], ids, row);
+    r.scale = ssm_map_operand(d.scale, ids, row);
+    return r;
+}
+static int ssm_op_count(const wsmc_ssm_stmt* s, int n) {   // 2 a SAMPLE (its Resample's too), 1 an OBSERVE
+    int ops = 0;
+    for (int q = 0; q < n; ++q) ops += s[q].kind == WSMC_SSM_SAMPLE ? 2 : s[q].kind == WSMC_SSM_OBSERVE ? 1 : 0;
+    return ops;
+}
+static int ssm_last_observe(const wsmc_ssm_spec* sp) {
+    int last = -1;
+    for (int q = 0; q < sp->n_step; ++q)
+        if (sp->step[q].kind == WSMC_SSM_OBSERVE) last = q;
+    return last;
+}
+
+// one statement through the operators, with its auto-inserted Resample. ess_out: wait on that
+// Resample for its ESS% (the trace), else it stays asynchronous
+static int ssm_issue(wsmc_ctx* c, const wsmc_ssm_stmt& s, const int32_t* ids, const double* row, double ess_min,
+                     int32_t scheme, double* ess_out) {
+    int rc;
+    switch (s.kind) {
+        case WSMC_SSM_SAMPLE: {
+            const wsmc_dist d = ssm_map_dist(s.dist, ids, row);
+            if ((rc = wsmc_sample(c, ids[s.col], &d))) return rc;
+            return wsmc_resample(c, ess_min, scheme, nullptr, nullptr);
+        }
+        case WSMC_SSM_ASSIGN: {
+            wsmc_operand e[4];
+            for (int k = 0; k < 4; ++k) e[k] = ssm_map_operand(s.value, ids, row);
+            return wsmc_assign(c, ids[s.col], e);
+        }
+        case WSMC_SSM_ASSIGN_EXPR: {
+            wsmc_xinst prog[WSMC_SSM_XPROG_MAX];
+            for (int q = 0; q < s.prog_len; ++q) {
+                prog[q] = s.prog[q];
+                if (prog[q].op != WSMC_X_COL) continue;
+                if (prog[q].col == WSMC_OPERAND_DATA) {
+                    prog[q].op = WSMC_X_CONST;
+                    prog[q].c = row[prog[q].comp];
+                    prog[q].col = -1;
+                    prog[q].comp = 0;
+                } else {
+                    prog[q].col = ids[prog[q].col];
+                }
+            }
+            const int32_t len[4] = {s.prog_len, 0, 0, 0};
+            return wsmc_assign_expr(c, ids[s.col], prog, len);
+        }
+        default: {
+            const wsmc_dist d = ssm_map_dist(s.dist, ids, row);
+            wsmc_operand x[4];
+            for (int k = 0; k < 4; ++k) x[k] = ssm_map_operand(s.value, ids, row);
+            if ((rc = wsmc_observe(c, &d, x))) return rc;
+            int32_t rs = 0;
+            return wsmc_resample(c, ess_min, scheme, ess_out ? &rs : nullptr, ess_out);
+        }
+    }
+}
+// the statement route: the spec's statements as a loop over the operators (any handle, any N, any
+// scheme); it is the definition of the run's results
+static int ssm_statements(wsmc_ctx* c, const wsmc_ssm_spec* sp, const int32_t* ids, const double* data, int32_t T,
+                          double ess_min, int32_t scheme, double* ess_trace) {
+    int rc;
+    for (int q = 0; q < sp->n_init; ++q)
+        if ((rc = ssm_issue(c, sp->init[q], ids, nullptr, ess_min, scheme, nullptr))) return rc;
+    const int last = ssm_last_observe(sp);
+    for (int32_t t = 0; t < T; ++t) {
+        const double* row = data ? data + (size_t)t * sp->data_dim : nullptr;
+        for (int q = 0; q < sp->n_step; ++q)
+            if ((rc = ssm_issue(c, sp->step[q], ids, row, ess_min, scheme, ess_trace && q == last ? ess_trace + t : nullptr)))
+                return rc;
+    }
+    return wsmc_sync(c);
+}
+
+// a statement as the kernel reads it; its program's instructions go to ins[*nins ...]
+static SsmStmt ssm_dev_stmt(const wsmc_ssm_stmt& s, SsmIns* ins, int* nins) {
+    SsmStmt r;
+    std::memset(&r, 0, sizeof(r));
+    r.kind = s.kind;
+    r.col = s.col;
+    r.mu.col[0] = r.mu.col[1] = r.scale.col[0] = r.scale.col[1] = r.value.col[0] = r.value.col[1] = -1;
+    if (s.kind == WSMC_SSM_SAMPLE || s.kind == WSMC_SSM_OBSERVE) {
+        r.family = s.dist.family;
+        r.mu = s.dist.mu[0];
+        r.scale = s.dist.scale;
+        r.param[0] = s.dist.param[0];
+        r.param[1] = s.dist.param[1];
+    }
+    if (s.kind == WSMC_SSM_ASSIGN || s.kind == WSMC_SSM_OBSERVE) r.value = s.value;
+    if (s.kind == WSMC_SSM_ASSIGN_EXPR) {
+        r.prog = *nins;
+        r.prog_len = s.prog_len;
+        for (int q = 0; q < s.prog_len; ++q) {
+            SsmIns& I = ins[(*nins)++];
+            I.op = s.prog[q].op;
+            I.c = s.prog[q].c;
+            I.col = 0;
+            if (I.op == WSMC_X_COL) I.col = s.prog[q].col == WSMC_OPERAND_DATA ? -1 - s.prog[q].comp : s.prog[q].col;
+        }
+    }
+    return r;
+}
+
+int wsmc_ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int32_t T, double ess_min, int32_t scheme,
+                 double* log_evidence_out, double* ess_trace_out) {
+    if (!c) return fail(WSMC_EARG, "null context");
+    if (int rc = wsmc_ssm_spec_check(sp)) return rc;
+    if (T < 1 || (sp->data_dim > 0 && !data)) return fail(WSMC_EARG, "bad arguments");
+    if (!valid_scheme(scheme)) return fail(WSMC_EARG, "unknown resampling scheme");
+    using clk = std::chrono::steady_clock;
+    auto us = [](clk::time_point t0, clk::time_point t1) {
+        return (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count();
+    };
+    const auto t_in = clk::now();
+    wsmc_ctx* sc = c->multi ? multi_first(c) : c;   // the counters' holder
+    const int S = sp->n_cols;
+    int32_t ids[WSMC_SSM_MAX_COLS] = {-1, -1, -1, -1};
+    for (int k = 0; k < S; ++k) {   // before any state changes: a spec column that exists must be a scalar
+        if (int rc = wsmc_col_find(c, sp->col_names[k], &ids[k])) return rc;
+        if (ids[k] < 0) continue;
+        int32_t dim = 0;
+        if (int rc = wsmc_col_info(c, ids[k], nullptr, 0, &dim)) return rc;
+        if (dim != 1) return fail(WSMC_EARG, std::string("ssm spec: column ") + sp->col_names[k] + " exists with dim != 1");
+    }
+    int nprog = 0;
+    unsigned feat = 0;
+    for (int q = 0; q < sp->n_init + sp->n_step; ++q) {
+        const wsmc_ssm_stmt& s = q < sp->n_init ? sp->init[q] : sp->step[q - sp->n_init];
+        if (s.kind == WSMC_SSM_ASSIGN_EXPR) nprog += s.prog_len;
+        if (s.kind == WSMC_SSM_SAMPLE || s.kind == WSMC_SSM_OBSERVE) feat |= wsmc_dist_feat(&s.dist);
+    }
+    // the persistent workgroup: one unsharded context, N within the cap for S columns, a stratified
+    // / systematic scheme, no column but the spec's, the weights unchanged (so a Resample after a
+    // SAMPLE never runs), and the programs within the kernel's arguments
+    bool persistent = !c->multi && !is_sharded(c) && c->N <= ssm_cap(S) && scheme != WSMC_RESAMPLE_MULTINOMIAL &&
+                      !c->weights_changed && nprog <= kSsmProgMax;
+    if (persistent)
+        for (const auto& col : c->cols) {
+            bool in = false;
+            for (int k = 0; k < S; ++k) in |= col.name == sp->col_names[k];
+            persistent &= in;
+        }
+    for (int k = 0; k < S; ++k)   // the missing ones, in order
+        if (int rc = wsmc_col_create(c, sp->col_names[k], 1, &ids[k])) return rc;
+    if (!persistent) {
+        int rc = ssm_statements(c, sp, ids, data, T, ess_min, scheme, ess_trace_out);
+        if (rc) return rc;
+        sc->ssm_stmt_runs += 1;
+        sc->ssm_book_us = 0;
+        if (log_evidence_out && (rc = wsmc_log_evidence(c, log_evidence_out))) return rc;
+        sc->ssm_wall_us = us(t_in, clk::now());
+        return WSMC_OK;
+    }
+    CHECK_CTX(c);   // an asynchronous run, the open statement batch, unstored Samples, a pending reset
+    if (int rc = resolve_decisions(c)) return rc;
+    if (int rc = check_deferred(c)) return rc;
+    scores_invalidate(c);   // the run rewrites the columns the tape reads
+    if (int rc = materialize(c, nullptr)) return rc;   // `init` may read a column a lazy Resample left behind
+    c->wseq += 1;           // ... and the weights
+    const int dd = sp->data_dim;
+    const int64_t ndata = (int64_t)T * dd;
+    if (c->lg_data_cap < ndata) {
+        WSMC_HIP(ctx_sync(c, c->stream));
+        if (c->lg_data) WSMC_HIP(hipFree(c->lg_data));
+        c->lg_data = nullptr;
+        c->lg_data_cap = 0;
+        WSMC_HIP(hipMalloc(&c->lg_data, sizeof(double) * (size_t)ndata));
+        c->lg_data_cap = ndata;
+    }
+    if (ess_trace_out && c->lg_trace_cap < T) {
+        WSMC_HIP(ctx_sync(c, c->stream));
+        if (c->lg_trace) WSMC_HIP(hipFree(c->lg_trace));
+        c->lg_trace = nullptr;
+        c->lg_trace_cap = 0;
+        WSMC_HIP(hipMalloc(&c->lg_trace, sizeof(double) * (size_t)T));
+        c->lg_trace_cap = T;
+    }
+    if (!c->lg_rec) WSMC_HIP(hipMalloc(&c->lg_rec, sizeof(LgRecord)));
+    if (ndata > 0)
+        WSMC_HIP(hipMemcpyAsync(c->lg_data, data, sizeof(double) * (size_t)ndata, hipMemcpyHostToDevice, c->stream));
+    WSMC_HIP(hipMemsetAsync(c->lg_rec, 0, sizeof(LgRecord), c->stream));
+    SsmArgs ka;
+    std::memset(&ka, 0, sizeof(ka));
+    for (int k = 0; k < S; ++k) ka.x[k] = c->cols[ids[k]].front;
+    ka.w = c->w;
+    ka.anc = c->anc;
+    ka.data = c->lg_data;
+    ka.ess_trace = ess_trace_out ? c->lg_trace : nullptr;
+    ka.rec = c->lg_rec;
+    ka.N = (int32_t)c->N;
+    const int threads = ssm_threads(feat, (int)c->N);
+    ka.P = (int32_t)((c->N + threads - 1) / threads);
+    ka.S = S;
+    ka.data_dim = dd;
+    ka.scheme = scheme;
+    ka.n_init = sp->n_init;
+    ka.n_step = sp->n_step;
+    ka.init_ops = ssm_op_count(sp->init, sp->n_init);
+    ka.step_ops = ssm_op_count(sp->step, sp->n_step);
+    ka.last_obs = ssm_last_observe(sp);
+    ka.seed = c->seed;
+    ka.op_base = c->op;
+    ka.ess_min = ess_min;
+    int nins = 0;
+    for (int q = 0; q < sp->n_init; ++q) ka.init[q] = ssm_dev_stmt(sp->init[q], ka.ins, &nins);
+    for (int q = 0; q < sp->n_step; ++q) ka.step[q] = ssm_dev_stmt(sp->step[q], ka.ins, &nins);
+    // every segment back to back on the stream; the state between them is the columns, w, anc and rec
+    const int32_t K = c->ssm_segment > 0 ? c->ssm_segment
+                                         : std::max(1, kSsmSegmentStmts / sp->n_step * 2 / std::max(2, (int)ka.P));
+    int64_t nseg = 0;
+    for (int32_t t0 = 0; t0 < T; t0 += K, ++nseg) {
+        ka.t0 = t0;
+        ka.nsteps = std::min<int32_t>(K, T - t0);
+        ka.first = t0 == 0;
+        WSMC_HIP(launch_ssm_segment(c->stream, ka, feat, threads));
+    }
+    LgRecord hrec;
+    WSMC_HIP(hipMemcpyAsync(&hrec, c->lg_rec, sizeof(LgRecord), hipMemcpyDeviceToHost, c->stream));
+    if (ess_trace_out)
+        WSMC_HIP(hipMemcpyAsync(ess_trace_out, c->lg_trace, sizeof(double) * (size_t)T, hipMemcpyDeviceToHost,
+                                c->stream));
+    // the bookkeeping of the statements issued one by one, while the device runs
+    const auto t_book = clk::now();
+    for (int k = 0; k < S; ++k) wrote_col(c, ids[k]);
+    gc_log(c);
+    int nterm_init = 0, nterm_step = 0;
+    for (int q = 0; q < sp->n_init; ++q) nterm_init += sp->init[q].kind == WSMC_SSM_SAMPLE || sp->init[q].kind == WSMC_SSM_OBSERVE;
+    for (int q = 0; q < sp->n_step; ++q) nterm_step += sp->step[q].kind == WSMC_SSM_SAMPLE || sp->step[q].kind == WSMC_SSM_OBSERVE;
+    c->tape.reserve(c->tape.size() + (size_t)nterm_init + (size_t)nterm_step * (size_t)T);
+    auto book = [&](const wsmc_ssm_stmt& s, const double* row) {
+        if (s.kind == WSMC_SSM_SAMPLE) {
+            push_sample_term(c, ids[s.col], ssm_map_dist(s.dist, ids, row));
+        } else if (s.kind == WSMC_SSM_OBSERVE) {
+            wsmc_term ob;
+            std::memset(&ob, 0, sizeof(ob));
+            ob.dist = ssm_map_dist(s.dist, ids, row);
+            for (int k = 0; k < 4; ++k) ob.x[k] = ssm_map_operand(s.value, ids, row);
+            ob.kind = WSMC_TERM_OBSERVE;
+            ob.depth = c->depth;
+            c->tape.push_back(ob);
+        }
+        c->depth += 1;   // an Assign's too
+    };
+    for (int q = 0; q < sp->n_init; ++q) book(sp->init[q], nullptr);
+    for (int32_t t = 0; t < T; ++t) {
+        const double* row = dd > 0 ? data + (size_t)t * dd : nullptr;
+        for (int q = 0; q < sp->n_step; ++q) book(sp->step[q], row);
+    }
+    c->op += (uint64_t)ka.init_ops + (uint64_t)ka.step_ops * (uint64_t)T;
+    c->weights_changed = 0;
+    const auto t_booked = clk::now();
+    WSMC_HIP(ctx_sync(c, c->stream));
+    c->resampled = hrec.last_dec;
+    c->last_ess = hrec.last_ess;
+    c->n_resamples += hrec.nres;
+    if (hrec.nres) set_anc_last(c, nullptr, -1);   // the last resampling step's row is in c->anc
+    c->wseq += 1;
+    c->ssm_runs += 1;
+    c->ssm_segments += nseg;
+    c->ssm_book_us = us(t_book, t_booked);
+    if (log_evidence_out)
+        if (int rc = wsmc_log_evidence(c, log_evidence_out)) return rc;
+    c->ssm_wall_us = us(t_in, clk::now());
+    return WSMC_OK;
+}
+
+int wsmc_debug_ssm(wsmc_ctx* c, int32_t segment_steps, int64_t* stats_out) {
+    if (!c) return fail(WSMC_EARG, "null context");
+    wsmc_ctx* sc = c->multi ? multi_first(c) : c;
+    if (segment_steps >= 0) sc->ssm_segment = segment_steps;
+    if (stats_out) {
+        for (int S = 1; S <= WSMC_SSM_MAX_COLS; ++S) stats_out[S - 1] = ssm_cap(S);
+        stats_out[4] = sc->ssm_runs;
+        stats_out[5] = sc->ssm_stmt_runs;
+        stats_out[6] = sc->ssm_segments;
+        stats_out[7] = sc->ssm_book_us;
+        stats_out[8] = sc->ssm_wall_us;
+    }
+    return WSMC_OK;
+}
+
 }  // extern "C"
 
 int wsmc_debug_jit_stats(int64_t* stats_out) {

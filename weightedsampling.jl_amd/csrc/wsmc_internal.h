@@ -379,6 +379,10 @@ struct wsmc_ctx {
     int32_t lg_segment = 0;                 // steps per launch (0: kLgSegmentSteps)
     int64_t lg_runs = 0, lg_stmt_runs = 0, lg_segments = 0;   // cumulative (wsmc_debug_lgssm)
     int64_t lg_book_us = 0, lg_wall_us = 0; // the last run's host bookkeeping / whole call, microseconds
+    // fused run of a specified scalar SSM (wsmc_ssm_run; it shares lg_data, lg_trace and lg_rec)
+    int32_t ssm_segment = 0;                // steps per launch (0: kSsmSegmentStmts / the step's statements)
+    int64_t ssm_runs = 0, ssm_stmt_runs = 0, ssm_segments = 0;   // cumulative (wsmc_debug_ssm)
+    int64_t ssm_book_us = 0, ssm_wall_us = 0;
     bool timing = false;
     std::vector<hipEvent_t> events;
     wsmc_run_timing last_timing{};
@@ -902,6 +906,63 @@ struct LgArgs {
 };
 size_t lgssm_lds_bytes(int n);
 hipError_t launch_lgssm_segment(hipStream_t s, const LgArgs& a, int threads);
+// fused run of a caller-specified scalar SSM (csrc/wsmc_ssm.hip, wsmc_ssm_run): the LGSSM
+// kernel's layout with S state columns. Per particle S + 1 column buffers (the spare takes one
+// column's gather at a time and is the u64 CDF during a Resample), the log-weight (8 B each) and
+// an ancestor (4 B): 8 (S + 2) + 4 bytes. The workgroup's 160 KiB less the 4 KiB of log / exp
+// tables and 2 KiB kept for the reduction scratch (1 KiB) and alignment leave 154 KiB; the cap
+// is the largest multiple of 64 particles (whole waves) that fits, and no more than the LGSSM
+// kernel's 5120: 5120 / 4352 / 3584 / 3008 for S = 1 .. 4.
+constexpr int kSsmLdsBudget = 160 * 1024 - 4096 - 2048;
+constexpr int ssm_cap(int S) {
+    const int n = (kSsmLdsBudget / (8 * (S + 2) + 4)) & ~63;
+    return n < kLgCap ? n : kLgCap;
+}
+constexpr int kSsmProgMax = WSMC_XPROG_MAX;   // program instructions the kernel's arguments hold
+// steps per launch by default, so that no launch runs longer than about 25 ms (the LGSSM kernel's
+// own bound): at N = 1000 (two particles a thread) the benchmark models measured 14.0 us a step
+// with 2 statements (the LGSSM spec) to 25.2 us with 4 (kitagawa, the heaviest), at most 7 us a
+// statement: 25 ms / 7 us = 3500 statements a launch, divided by the step's statements and by the
+// particles a thread holds beyond two
+constexpr int kSsmSegmentStmts = 3500;
+struct SsmStmt {                 // one statement as the kernel reads it (kernel arguments)
+    int32_t kind, col;           // wsmc_ssm_kind; the output column (local index)
+    int32_t prog, prog_len;      // ASSIGN_EXPR: its instructions [prog, prog + prog_len) of SsmArgs::ins
+    int32_t family, pad;         // SAMPLE / OBSERVE: the dist, its operands over local indices
+    wsmc_operand mu, scale;
+    double param[2];
+    wsmc_operand value;          // ASSIGN: the right-hand side; OBSERVE: the observed value
+};
+struct SsmIns {                  // wsmc_xinst over local column indices
+    int32_t op;
+    int32_t col;                 // WSMC_X_COL: the local index, or -1 - j for data[t][j]
+    double c;
+};
+struct SsmArgs {
+    double* x[WSMC_SSM_MAX_COLS];   // [N] each: the columns (read at the segment's start, written at its end)
+    double* w;                // [N] log-weights
+    int32_t* anc;             // [N] written when a step of the segment resampled
+    const double* data;       // [T x data_dim] row-major
+    double* ess_trace;        // [T] or null
+    LgRecord* rec;
+    int32_t N, P;             // particles, particles per thread
+    int32_t S, data_dim;      // columns
+    int32_t t0, nsteps;       // the segment's steps [t0, t0 + nsteps)
+    int32_t first, scheme;    // first: the segment starts the run (it runs `init`)
+    int32_t n_init, n_step;
+    int32_t init_ops, step_ops;   // op counters `init` / one step take (2 a SAMPLE, 1 an OBSERVE)
+    int32_t last_obs, pad;    // the step's last OBSERVE (its Resample's ESS% is the trace's)
+    uint64_t seed, op_base;   // op_base: the op counter at the run's start
+    double ess_min;
+    SsmStmt init[WSMC_SSM_MAX_INIT];
+    SsmStmt step[WSMC_SSM_MAX_STMTS];
+    SsmIns ins[kSsmProgMax];
+};
+static_assert(sizeof(SsmArgs) + 32 <= 4096, "the spec rides in the kernel arguments");
+size_t ssm_lds_bytes(int n, int S);
+// feat: WSMC_FEAT_EXT / WSMC_FEAT_GAM bits over the spec's dists (the kernel's instantiation)
+int ssm_threads(unsigned feat, int n);
+hipError_t launch_ssm_segment(hipStream_t s, const SsmArgs& a, unsigned feat, int threads);
 // one handle over several devices (wsmc_multi.hip): the ABI entry points fan out
 int multi_destroy(wsmc_ctx* c);
 wsmc_ctx* multi_first(wsmc_ctx* c);

@@ -755,4 +755,88 @@ function lgssm1d_run!(state::HipState, data::AbstractVector; a=0.9, q=1.0, r=0.5
     return ess_trace ? (ev[], tr) : ev[]
 end
 
+# wsmc_ssm_stmt / wsmc_ssm_spec (include/wsmc.h): a scalar state-space model for wsmc_ssm_run.
+# isbits, the C layout: 32 program slots a statement, 4 names of 32 bytes, 4 init and 8 step slots.
+struct WsmcSsmStmt
+    kind::Int32
+    col::Int32
+    prog_len::Int32
+    reserved::Int32
+    dist::WsmcDist
+    value::WsmcOperand
+    prog::NTuple{32,WsmcXInst}
+end
+struct WsmcSsmSpec
+    n_cols::Int32
+    data_dim::Int32
+    n_init::Int32
+    n_step::Int32
+    col_names::NTuple{4,NTuple{32,UInt8}}
+    init::NTuple{4,WsmcSsmStmt}
+    step::NTuple{8,WsmcSsmStmt}
+end
+const SSM_SAMPLE, SSM_ASSIGN, SSM_ASSIGN_EXPR, SSM_OBSERVE = Int32(0), Int32(1), Int32(2), Int32(3)
+const OPERAND_DATA = Int32(-2)   # col of an operand slot / a program's COL: column comp of the data table
+
+const _NO_INST = WsmcXInst(Int32(0), Int32(-1), Int32(0), Int32(0), 0.0)
+const _NO_DIST = WsmcDist(FAM_NORMAL, MEAN_AFFINE, Int32(1), Int32(0), ntuple(_ -> const_operand(0.0), 4),
+                          const_operand(1.0), (0.0, 0.0))
+_prog32(prog) = ntuple(k -> k <= length(prog) ? prog[k] : _NO_INST, 32)
+"`col ~ dist` (operands over the spec's local column indices, `OPERAND_DATA` for the step's data)"
+ssm_sample(col::Integer, dist::WsmcDist) =
+    WsmcSsmStmt(SSM_SAMPLE, Int32(col), Int32(0), Int32(0), dist, const_operand(0.0), _prog32(()))
+"`col .= value` (an operand)"
+ssm_assign(col::Integer, value::WsmcOperand) =
+    WsmcSsmStmt(SSM_ASSIGN, Int32(col), Int32(0), Int32(0), _NO_DIST, value, _prog32(()))
+"`col .= program` (a postfix program of at most 32 `WsmcXInst`)"
+ssm_assign(col::Integer, prog::AbstractVector{WsmcXInst}) =
+    WsmcSsmStmt(SSM_ASSIGN_EXPR, Int32(col), Int32(length(prog)), Int32(0), _NO_DIST, const_operand(0.0), _prog32(prog))
+"`value => dist`"
+ssm_observe(value::WsmcOperand, dist::WsmcDist) =
+    WsmcSsmStmt(SSM_OBSERVE, Int32(-1), Int32(0), Int32(0), dist, value, _prog32(()))
+
+"""
+    ssm_spec(cols, init, step; data_dim=1) -> WsmcSsmSpec
+
+The model description of `wsmc_ssm_run`: 1..4 scalar column names, at most 4 `init` and 8 `step`
+statements built with `ssm_sample`, `ssm_assign` and `ssm_observe`.
+"""
+function ssm_spec(cols::AbstractVector{<:AbstractString}, init::AbstractVector{WsmcSsmStmt},
+                  step::AbstractVector{WsmcSsmStmt}; data_dim::Integer=1)
+    1 <= length(cols) <= 4 && length(init) <= 4 && 1 <= length(step) <= 8 ||
+        throw(ArgumentError("1..4 columns, at most 4 init and 1..8 step statements"))
+    name(k) = (b = k <= length(cols) ? codeunits(cols[k]) : UInt8[];
+               length(b) < 32 || throw(ArgumentError("column name too long"));
+               ntuple(j -> j <= length(b) ? b[j] : 0x00, 32))
+    pad = ssm_assign(0, const_operand(0.0))
+    spec = WsmcSsmSpec(Int32(length(cols)), Int32(data_dim), Int32(length(init)), Int32(length(step)),
+                       ntuple(name, 4), ntuple(k -> k <= length(init) ? init[k] : pad, 4),
+                       ntuple(k -> k <= length(step) ? step[k] : pad, 8))
+    check(ccall((:wsmc_ssm_spec_check, libwsmc), Cint, (Ref{WsmcSsmSpec},), spec))
+    return spec
+end
+
+"""
+    ssm_run!(state, spec, data; scheme, ess_trace=false) -> log_evidence[, trace]
+
+A scalar state-space model the caller specifies as one call (`wsmc_ssm_run`), beside
+`lgssm1d_run!`: `data` is a vector (one data column) or a T x data_dim matrix. The columns,
+weights, flags and RNG positions are those of `run!` of the same statements. A population within
+the persistent kernel's cap for the spec's column count runs on one workgroup with no launch per
+step; every other shape issues the statements inside the library. (Written against the C ABI; not
+run in this repository's checks, which have no Julia.)
+"""
+function ssm_run!(state::HipState, spec::WsmcSsmSpec, data::AbstractVecOrMat; scheme=RESAMPLE_STRATIFIED,
+                  ess_trace=false)
+    T = size(data, 1)
+    d = Vector{Float64}(vec(permutedims(reshape(Float64.(data), T, :))))   # row-major T x data_dim
+    ev = Ref{Float64}(0.0)
+    tr = ess_trace ? Vector{Float64}(undef, T) : Float64[]
+    check(ccall((:wsmc_ssm_run, libwsmc), Cint,
+                (Ptr{Cvoid}, Ref{WsmcSsmSpec}, Ptr{Float64}, Int32, Float64, Int32, Ptr{Float64}, Ptr{Float64}),
+                state.store.ctx, spec, d, T, state.ess_perc_min, scheme, ev, ess_trace ? tr : C_NULL))
+    mirror_flags!(state)
+    return ess_trace ? (ev[], tr) : ev[]
+end
+
 end # module

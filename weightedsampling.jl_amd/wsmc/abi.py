@@ -92,6 +92,25 @@ class MoveSpec(C.Structure):
                 ("lo", C.c_double * 4), ("hi", C.c_double * 4)]
 
 
+# wsmc_ssm_spec (include/wsmc.h): a scalar state-space model for wsmc_ssm_run
+SSM_MAX_COLS, SSM_MAX_INIT, SSM_MAX_STMTS, SSM_MAX_DATA, SSM_XPROG_MAX, SSM_NAME_MAX = 4, 4, 8, 4, 32, 32
+OPERAND_DATA = -2
+SSM_SAMPLE, SSM_ASSIGN, SSM_ASSIGN_EXPR, SSM_OBSERVE = range(4)
+
+
+class SsmStmt(C.Structure):
+    """wsmc_ssm_stmt: one statement of a wsmc_ssm_spec"""
+    _fields_ = [("kind", C.c_int32), ("col", C.c_int32), ("prog_len", C.c_int32), ("reserved", C.c_int32),
+                ("dist", Dist), ("value", Operand), ("prog", XInst * SSM_XPROG_MAX)]
+
+
+class SsmSpec(C.Structure):
+    """wsmc_ssm_spec: the columns, the `init` list and the `step` list"""
+    _fields_ = [("n_cols", C.c_int32), ("data_dim", C.c_int32), ("n_init", C.c_int32), ("n_step", C.c_int32),
+                ("col_names", (C.c_char * SSM_NAME_MAX) * SSM_MAX_COLS),
+                ("init", SsmStmt * SSM_MAX_INIT), ("step", SsmStmt * SSM_MAX_STMTS)]
+
+
 class RunTiming(C.Structure):
     _fields_ = [("total_ms", C.c_double), ("propagate_ms", C.c_double),
                 ("reduce_ms", C.c_double), ("resample_ms", C.c_double),
@@ -162,6 +181,10 @@ SIGNATURES = {
     "wsmc_lgssm1d_run": (C.c_int, [_P, _D, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                    C.c_int32, _D, _D]),
     "wsmc_debug_lgssm": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int64)]),
+    "wsmc_ssm_spec_check": (C.c_int, [C.POINTER(SsmSpec)]),
+    "wsmc_ssm_spec_sizeof": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "wsmc_ssm_run": (C.c_int, [_P, C.POINTER(SsmSpec), _D, C.c_int32, C.c_double, C.c_int32, _D, _D]),
+    "wsmc_debug_ssm": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int64)]),
     "wsmc_run_set_timing": (C.c_int, [_P, C.c_int32]),
     "wsmc_run_get_timing": (C.c_int, [_P, C.POINTER(RunTiming)]),
     "wsmc_debug_kernel_bench": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _D]),

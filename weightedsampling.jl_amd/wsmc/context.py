@@ -457,6 +457,37 @@ class Context:
             raise ValueError("steps must be >= 0")
         check(self._L.wsmc_debug_lgssm(self._h, int(steps), None))
 
+    def ssm_run(self, spec, data, ess_perc_min=1.0, scheme: int = abi.RESAMPLE_STRATIFIED,
+                want_evidence: bool = True, ess_trace: bool = False, T: int | None = None):
+        """A scalar state-space model (wsmc.SSM) as one call (wsmc_ssm_run): the same columns,
+        weights, ancestors, state, tape and RNG positions as spec.statements(self, data, ...).
+        data: T values, or T rows of the spec's data columns (a spec that reads no data takes T).
+        Returns the log evidence (None without want_evidence), or (evidence, trace) with
+        ess_trace: the ESS% of the Resample after each step's last observe."""
+        tab = spec.table(data, T)
+        ev = C.c_double()
+        tr = np.empty(len(tab)) if ess_trace else None
+        check(self._L.wsmc_ssm_run(self._h, C.byref(spec.spec), _dptr(tab) if tab.size else None, len(tab),
+                                   float(ess_perc_min), int(scheme), C.byref(ev) if want_evidence else None,
+                                   _dptr(tr) if ess_trace else None))
+        e = float(ev.value) if want_evidence else None
+        return (e, tr) if ess_trace else e
+
+    def ssm_stats(self) -> dict:
+        """wsmc_debug_ssm's counters: the persistent kernel's particle cap for 1..4 columns, the runs
+        it took, the runs that went through the statement route, the segments launched
+        (cumulative), and the last run's host bookkeeping and whole-call seconds."""
+        st = (C.c_int64 * 9)()
+        check(self._L.wsmc_debug_ssm(self._h, -1, st))
+        return {"cap": {S: int(st[S - 1]) for S in range(1, 5)}, "persistent_runs": st[4], "statement_runs": st[5],
+                "segments": st[6], "bookkeeping_s": st[7] / 1e6, "call_s": st[8] / 1e6}
+
+    def set_ssm_segment(self, steps: int) -> None:
+        """Steps per launch of the persistent SSM kernel (0 restores the default)."""
+        if steps < 0:
+            raise ValueError("steps must be >= 0")
+        check(self._L.wsmc_debug_ssm(self._h, int(steps), None))
+
     def set_timing(self, enabled: bool) -> None:
         check(self._L.wsmc_run_set_timing(self._h, int(bool(enabled))))
 

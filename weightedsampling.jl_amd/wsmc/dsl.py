@@ -8,6 +8,7 @@ to two column components (``α + β * x``, ``a .* x``, ``x{t} + v``).
 
     Col("x")            column x (component 0)
     Col("x", 1)         component 1 of a vector column
+    Data(0)             column 0 of a fused state-space run's data table (wsmc.SSM)
     2.0 * Col("x") + 1  affine forms
     Normal(mu, sigma), MvNormal(mu, cov), HalfNormal(sigma), Uniform(a, b)
     Oscillator(t, A, ω, γ, ϕ)  the damped-oscillator mean (examples/damped_oscillator.jl:11)
@@ -157,6 +158,18 @@ class Expr:
 
 def Col(name: str, comp: int = 0) -> Expr:
     return Expr(0.0, ((str(name), int(comp), 1.0),))
+
+
+# the "column" name of a data reference (no real column can carry it: a NUL ends a C name)
+DATA = "\x00data"
+
+
+def Data(j: int = 0) -> Expr:
+    """Column j of a fused state-space run's data table at the current step (wsmc.SSM,
+    include/wsmc.h WSMC_OPERAND_DATA): usable wherever Col is inside an SSM's `step`. In an
+    operand it must stand alone as the constant part (`Data(0)`, `Data(0) + 2 * Col("x")`), so
+    that folding the step's value into c0 is exact; inside a general expression it is a leaf."""
+    return Expr(0.0, ((DATA, int(j), 1.0),))
 
 
 def _exprs(v, dim: int) -> list[Expr]:

@@ -222,6 +222,121 @@ def lgssm1d_data(T: int, a=0.9, q=1.0, r=0.5, x0_std=1.0, seed: int = 42):
     return obs
 
 
+# ---------------------------------------------------------------------------------------
+# scalar state-space models as specs (wsmc.SSM): Context.ssm_run runs one in a single call,
+# spec.statements issues the same statements one by one on a Context or the oracle
+def lgssm1d_spec(a=0.9, q=1.0, r=0.5, x0_std=1.0):
+    """lgssm1d_statements as a spec: x ~ Normal(0, x0_std); step: x ~ Normal(a x, q); y_t => Normal(x, r)."""
+    from .dsl import Data
+    from .ssm import SSM, observe, sample
+    return (SSM(cols=["x"])
+            .init(sample("x", Normal(0.0, x0_std)))
+            .step(sample("x", Normal(Col("x") * a, q)),
+                  observe(Data(0), Normal(Col("x"), r))))
+
+
+def sv(mu=-1.0, phi=0.95, sigma=0.25):
+    """Stochastic volatility: h ~ Normal(0, sigma / sqrt(1 - phi^2)); step: h ~ Normal(mu (1 - phi) +
+    phi h, sigma); s .= exp(h / 2); y_t => Normal(0, s)."""
+    from . import dsl
+    from .ssm import SSM, assign, observe, sample
+    return (SSM(cols=["h", "s"])
+            .init(sample("h", Normal(0.0, sigma / math.sqrt(1.0 - phi * phi))))
+            .step(sample("h", Normal(Col("h") * phi + mu * (1.0 - phi), sigma)),
+                  assign("s", dsl.exp(Col("h") / 2)),
+                  observe(dsl.Data(0), Normal(0.0, Col("s")))))
+
+
+def poisson_count(a=0.9, sigma=0.3, x0_std=0.5):
+    """A count series: x ~ Normal(0, x0_std); step: x ~ Normal(a x, sigma); rate .= exp(x);
+    y_t => Poisson(rate)."""
+    from . import dsl
+    from .ssm import SSM, assign, observe, sample
+    return (SSM(cols=["x", "rate"])
+            .init(sample("x", Normal(0.0, x0_std)))
+            .step(sample("x", Normal(Col("x") * a, sigma)),
+                  assign("rate", dsl.exp(Col("x"))),
+                  observe(dsl.Data(0), dsl.Poisson(Col("rate")))))
+
+
+def kitagawa(q=math.sqrt(10.0), r=1.0, x0_std=math.sqrt(5.0)):
+    """The nonlinear benchmark with a known covariate u_t = 8 cos(1.2 t) (data column 1):
+    x ~ Normal(0, x0_std); step: m .= x / 2 + 25 x / (1 + x^2) + u_t; x ~ Normal(m, q);
+    z .= x^2 / 20; y_t => Normal(z, r)."""
+    from . import dsl
+    from .ssm import SSM, assign, observe, sample
+    x = Col("x")
+    return (SSM(cols=["x", "m", "z"])
+            .init(sample("x", Normal(0.0, x0_std)))
+            .step(assign("m", x / 2 + 25 * x / (1 + x ** 2) + dsl.Data(1)),
+                  sample("x", Normal(Col("m"), q)),
+                  assign("z", x ** 2 / 20),
+                  observe(dsl.Data(0), Normal(Col("z"), r))))
+
+
+def local_trend(q_v=0.05, q_x=0.3, r=0.5, v0_std=0.1, x0_std=1.0):
+    """A level with a trend, two Samples a step: v ~ Normal(0, v0_std); x ~ Normal(0, x0_std);
+    step: v ~ Normal(v, q_v); x ~ Normal(x + v, q_x); y_t => Normal(x, r)."""
+    from . import dsl
+    from .ssm import SSM, observe, sample
+    return (SSM(cols=["v", "x"])
+            .init(sample("v", Normal(0.0, v0_std)), sample("x", Normal(0.0, x0_std)))
+            .step(sample("v", Normal(Col("v"), q_v)),
+                  sample("x", Normal(Col("x") + Col("v"), q_x)),
+                  observe(dsl.Data(0), Normal(Col("x"), r))))
+
+
+def sv_data(T: int, mu=-1.0, phi=0.95, sigma=0.25, seed: int = 42):
+    """returns simulated from sv's own model on numpy's Philox stream"""
+    rng = np.random.Generator(np.random.Philox(seed))
+    h = sigma / math.sqrt(1.0 - phi * phi) * rng.standard_normal()
+    y = np.empty(T)
+    for t in range(T):
+        h = mu * (1.0 - phi) + phi * h + sigma * rng.standard_normal()
+        y[t] = math.exp(h / 2) * rng.standard_normal()
+    return y
+
+
+def poisson_count_data(T: int, a=0.9, sigma=0.3, x0_std=0.5, seed: int = 42):
+    """counts simulated from poisson_count's own model on numpy's Philox stream"""
+    rng = np.random.Generator(np.random.Philox(seed))
+    x = x0_std * rng.standard_normal()
+    y = np.empty(T)
+    for t in range(T):
+        x = a * x + sigma * rng.standard_normal()
+        y[t] = float(rng.poisson(math.exp(x)))
+    return y
+
+
+def kitagawa_data(T: int, q=math.sqrt(10.0), r=1.0, x0_std=math.sqrt(5.0), seed: int = 42):
+    """T x 2: the observation and the covariate u_t = 8 cos(1.2 t), t = 1..T, on numpy's Philox stream"""
+    rng = np.random.Generator(np.random.Philox(seed))
+    x = x0_std * rng.standard_normal()
+    out = np.empty((T, 2))
+    for t in range(T):
+        u = 8.0 * math.cos(1.2 * (t + 1))
+        x = x / 2 + 25 * x / (1 + x * x) + u + q * rng.standard_normal()
+        out[t] = (x * x / 20 + r * rng.standard_normal(), u)
+    return out
+
+
+def local_trend_data(T: int, q_v=0.05, q_x=0.3, r=0.5, v0_std=0.1, x0_std=1.0, seed: int = 42):
+    """observations simulated from local_trend's own model on numpy's Philox stream"""
+    rng = np.random.Generator(np.random.Philox(seed))
+    v, x = v0_std * rng.standard_normal(), x0_std * rng.standard_normal()
+    y = np.empty(T)
+    for t in range(T):
+        v = v + q_v * rng.standard_normal()
+        x = x + v + q_x * rng.standard_normal()
+        y[t] = x + r * rng.standard_normal()
+    return y
+
+
+# name -> (spec constructor, data generator) of the four models above
+SSM_MODELS = {"sv": (sv, sv_data), "poisson_count": (poisson_count, poisson_count_data),
+              "kitagawa": (kitagawa, kitagawa_data), "local_trend": (local_trend, local_trend_data)}
+
+
 def linreg_data(seed: int = 42):
     """examples/linear_regression.jl:31-33: xs = 1:10, ys = 1 - 0.5 xs + 0.5 z."""
     rng = np.random.Generator(np.random.Philox(seed))

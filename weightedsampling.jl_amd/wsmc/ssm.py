@@ -1,0 +1,245 @@
+"""Scalar state-space models the caller specifies (include/wsmc.h wsmc_ssm_spec, wsmc_ssm_run).
+
+    from wsmc import SSM, Col, Normal
+    from wsmc.dsl import Data, exp
+    from wsmc.ssm import sample, assign, observe
+
+    sv = (SSM(cols=["h", "s"])
+          .init(sample("h", Normal(0.0, 0.5)))
+          .step(sample("h", Normal(0.95 * Col("h"), 0.2)),
+                assign("s", exp(Col("h") / 2)),
+                observe(Data(0), Normal(0.0, Col("s")))))
+    ev = ctx.ssm_run(sv, y)                    # one call (a persistent workgroup where it fits)
+    sv.statements(ctx_or_oracle, y)            # the same statements, issued one by one
+
+Every `sample` and `observe` is followed by its auto-inserted Resample (what @model inserts); an
+`assign` whose right-hand side is affine in at most two columns lowers to WSMC_SSM_ASSIGN, every
+other one to WSMC_SSM_ASSIGN_EXPR (a postfix program). `Data(j)` is column j of the run's data
+table at the current step; only `step` may read it.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import abi
+from .abi import Operand
+from .dsl import DATA, Expr, Fx, Kernel, xprogram
+
+
+def sample(col: str, kernel: Kernel):
+    """col ~ kernel"""
+    return (abi.SSM_SAMPLE, str(col), kernel)
+
+
+def assign(col: str, rhs):
+    """col .= rhs"""
+    return (abi.SSM_ASSIGN, str(col), rhs)
+
+
+def observe(value, kernel: Kernel):
+    """value => kernel"""
+    return (abi.SSM_OBSERVE, value, kernel)
+
+
+def _general(rhs) -> bool:
+    """the right-hand side needs a program: an Fx, or an affine form whose merged operand would
+    round differently from the user's own order (Expr.fx)"""
+    return isinstance(rhs, Fx) or (isinstance(rhs, Expr) and rhs.fx is not None)
+
+
+class SSM:
+    """A builder for wsmc_ssm_spec: SSM(cols=[...]).init(...).step(...)."""
+
+    def __init__(self, cols, data_dim: int | None = None):
+        self.cols = [str(c) for c in cols]
+        self._init: list = []
+        self._step: list = []
+        self._data_dim = data_dim
+        self._spec = None
+
+    def init(self, *stmts) -> "SSM":
+        self._init += list(stmts)
+        self._spec = None
+        return self
+
+    def step(self, *stmts) -> "SSM":
+        self._step += list(stmts)
+        self._spec = None
+        return self
+
+    # ---- lowering ----
+    def _resolve(self, name):
+        if name == DATA:
+            return abi.OPERAND_DATA
+        try:
+            return self.cols.index(name)
+        except ValueError:
+            raise KeyError(f"unknown column {name!r} (the spec's columns are {self.cols})") from None
+
+    def _lower(self, st, out: abi.SsmStmt) -> None:
+        kind = st[0]
+        out.kind = kind
+        out.col = -1
+        out.value = Operand.const(0.0)
+        if kind == abi.SSM_SAMPLE:
+            out.col = self._resolve(st[1])
+            out.dist = st[2].dist(self._resolve)
+        elif kind == abi.SSM_OBSERVE:
+            out.value = Expr.lift(st[1]).operand(self._resolve)
+            out.dist = st[2].dist(self._resolve)
+        elif _general(st[2]):
+            out.kind = abi.SSM_ASSIGN_EXPR
+            out.col = self._resolve(st[1])
+            prog, lens = xprogram([st[2]], self._resolve)
+            if lens[0] > abi.SSM_XPROG_MAX:
+                raise ValueError(f"{st[1]}: a program of {lens[0]} instructions (at most {abi.SSM_XPROG_MAX})")
+            out.prog_len = lens[0]
+            for k in range(lens[0]):
+                out.prog[k] = prog[k]
+        else:
+            out.col = self._resolve(st[1])
+            out.value = Expr.lift(st[2]).operand(self._resolve)
+
+    @property
+    def spec(self) -> abi.SsmSpec:
+        """The wsmc_ssm_spec (built once; the builder's statements lowered over local indices)."""
+        if self._spec is not None:
+            return self._spec
+        if not 1 <= len(self.cols) <= abi.SSM_MAX_COLS:
+            raise ValueError(f"1..{abi.SSM_MAX_COLS} columns")
+        if len(self._init) > abi.SSM_MAX_INIT or len(self._step) > abi.SSM_MAX_STMTS:
+            raise ValueError(f"at most {abi.SSM_MAX_INIT} init and {abi.SSM_MAX_STMTS} step statements")
+        sp = abi.SsmSpec()
+        sp.n_cols = len(self.cols)
+        for k, name in enumerate(self.cols):
+            b = name.encode()
+            if len(b) >= abi.SSM_NAME_MAX:
+                raise ValueError(f"column name {name!r} longer than {abi.SSM_NAME_MAX - 1} bytes")
+            sp.col_names[k].value = b
+        sp.n_init, sp.n_step = len(self._init), len(self._step)
+        for k, st in enumerate(self._init):
+            self._lower(st, sp.init[k])
+        for k, st in enumerate(self._step):
+            self._lower(st, sp.step[k])
+        used = -1
+        for q in range(sp.n_init + sp.n_step):
+            s = sp.init[q] if q < sp.n_init else sp.step[q - sp.n_init]
+            ops = list(s.dist.mu) + [s.dist.scale, s.value]
+            for o in ops:
+                for k in range(2):
+                    if o.col[k] == abi.OPERAND_DATA:
+                        used = max(used, o.comp[k])
+            for k in range(s.prog_len):
+                if s.prog[k].op == abi.X_COL and s.prog[k].col == abi.OPERAND_DATA:
+                    used = max(used, s.prog[k].comp)
+        sp.data_dim = used + 1 if self._data_dim is None else int(self._data_dim)
+        self._spec = sp
+        return sp
+
+    def check(self) -> None:
+        """wsmc_ssm_spec_check (host only): raises WSMCError(WSMC_EARG) with the reason"""
+        abi.check(abi.load_library().wsmc_ssm_spec_check(C.byref(self.spec)))
+
+    def table(self, data, T: int | None = None) -> np.ndarray:
+        """the run's data as the T x data_dim table the C entry point takes (a spec that reads no
+        data takes its horizon from T, or from len(data))"""
+        dd = self.spec.data_dim
+        if dd == 0:
+            return np.empty((len(data) if T is None else int(T), 0))
+        return np.ascontiguousarray(np.asarray(data, dtype=np.float64).reshape(-1, dd))
+
+    # ---- the executable definition ----
+    def statements(self, backend, data, ess_perc_min: float = 1.0, scheme: int = abi.RESAMPLE_STRATIFIED,
+                   wait: bool = True, T: int | None = None):
+        """Issue the spec's statements one by one on `backend` (a Context or the tests' Oracle: any
+        object with the operator methods), each `sample` / `observe` followed by its Resample, the
+        step's data folded into constants: a data slot of an operand is removed and its value
+        becomes c0, a data read of a program becomes a constant. This is what wsmc_ssm_run
+        computes. wait=True returns (flags, ESS%) of the Resample after each step's last observe;
+        wait=False leaves every Resample asynchronous and returns None."""
+        sp = self.spec
+        tab = self.table(data, T)
+        T = len(tab)
+        ids = [backend.col_create(name, 1) for name in self.cols]
+
+        # every statement is built once (ids mapped, data slots removed); a step only writes its
+        # data values into the slots listed in `patch`: (object, field, data column)
+        def fold_operand(o, patch):
+            r = Operand()
+            C.memmove(C.byref(r), C.byref(o), C.sizeof(Operand))
+            for k in range(2):
+                if o.col[k] == abi.OPERAND_DATA:
+                    patch.append((r, "c0", int(o.comp[k])))
+                    r.col[k], r.comp[k], r.coef[k] = -1, 0, 0.0
+                elif o.col[k] >= 0:
+                    r.col[k] = ids[o.col[k]]
+            return r
+
+        def fold_dist(d, patch):
+            r = abi.Dist()
+            C.memmove(C.byref(r), C.byref(d), C.sizeof(abi.Dist))
+            for k in range(4):
+                ops = []
+                r.mu[k] = fold_operand(d.mu[k], ops)
+                patch += [(r.mu[k], f, j) for _, f, j in ops]   # (a view into r: the copy above is not)
+            ops = []
+            r.scale = fold_operand(d.scale, ops)
+            patch += [(r.scale, f, j) for _, f, j in ops]
+            return r
+
+        def prepare(s):
+            """(call, patch): call(waited) issues the statement and its Resample"""
+            patch = []
+            out = ids[s.col] if s.kind != abi.SSM_OBSERVE else -1
+            if s.kind == abi.SSM_SAMPLE:
+                d = fold_dist(s.dist, patch)
+
+                def call(waited):
+                    backend.sample(out, d)
+                    backend.resample(ess_perc_min, scheme, wait=False)
+            elif s.kind == abi.SSM_ASSIGN:
+                e = [fold_operand(s.value, patch)]
+
+                def call(waited):
+                    backend.assign(out, e)
+            elif s.kind == abi.SSM_ASSIGN_EXPR:
+                prog = (abi.XInst * s.prog_len)()
+                lens = [int(s.prog_len)]
+                for k in range(s.prog_len):
+                    prog[k] = s.prog[k]
+                    if prog[k].op != abi.X_COL:
+                        continue
+                    if prog[k].col == abi.OPERAND_DATA:
+                        patch.append((prog[k], "c", int(prog[k].comp)))
+                        prog[k].op, prog[k].col, prog[k].comp = abi.X_CONST, -1, 0
+                    else:
+                        prog[k].col = ids[prog[k].col]
+
+                def call(waited):
+                    backend.assign_expr(out, prog, lens)
+            else:
+                d = fold_dist(s.dist, patch)
+                x = [fold_operand(s.value, patch)]
+
+                def call(waited):
+                    backend.observe(d, x)
+                    return backend.resample(ess_perc_min, scheme, wait=waited)
+            return call, patch
+
+        for q in range(sp.n_init):
+            prepare(sp.init[q])[0](False)
+        last = max(q for q in range(sp.n_step) if sp.step[q].kind == abi.SSM_OBSERVE)
+        step = [prepare(sp.step[q]) for q in range(sp.n_step)]
+        flags, ess = [], []
+        for t in range(T):
+            row = tab[t]
+            for q, (call, patch) in enumerate(step):
+                for obj, field, j in patch:
+                    setattr(obj, field, row[j])
+                r = call(wait and q == last)
+                if wait and q == last:
+                    flags.append(bool(r[0]))
+                    ess.append(float(r[1]))
+        return (flags, np.array(ess)) if wait else None
