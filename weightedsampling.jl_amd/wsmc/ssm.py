@@ -59,6 +59,15 @@ class SSM:
         self._data_dim = data_dim
         self._spec = None
 
+    @classmethod
+    def from_spec(cls, spec: abi.SsmSpec) -> "SSM":
+        """A ready wsmc_ssm_spec (filled by hand: the operand forms the builder does not write,
+        such as a data slot behind a column) with everything but the builder: .spec, .cols,
+        .table, .check and .statements. The struct is used as it is, not copied or lowered."""
+        r = cls([spec.col_names[k].value.decode() for k in range(spec.n_cols)], data_dim=spec.data_dim)
+        r._spec = spec
+        return r
+
     def init(self, *stmts) -> "SSM":
         self._init += list(stmts)
         self._spec = None
