@@ -506,6 +506,49 @@ int wsmc_ssm_run(wsmc_ctx* ctx, const wsmc_ssm_spec* spec, const double* data, i
  * context), then the last run's host bookkeeping time (tape and state, done while the device
  * runs) and whole-call time, microseconds. */
 int wsmc_debug_ssm(wsmc_ctx* ctx, int32_t segment_steps, int64_t* stats_out);
+/* ---- many independent filters in one call ------------------------------------------------
+ * The results of a batch: caller-owned host buffers, each may be NULL (not wanted). */
+typedef struct {
+    double*  log_evidence;      /* [B] */
+    double*  ess_trace;         /* [B][T] the ESS% after each step's last OBSERVE (NaN kept) */
+    double*  cols;              /* [B][n_cols][n] the final columns, in the spec's order */
+    double*  log_weights;       /* [B][n] */
+    int32_t* last_ancestors;    /* [B][n] row b: the last resampling step's ancestors if n_resamples[b] > 0,
+                                   else zeros (wsmc_last_ancestors of a fresh context) */
+    int64_t* n_resamples;       /* [B] */
+    int32_t* last_resampled;    /* [B] the last Resample's decision */
+} wsmc_ssm_batch_out;
+/* B independent runs of wsmc_ssm_run in one call, one persistent workgroup per run, B workgroups
+ * a launch. Filter b is, bit for bit, what wsmc_ssm_run(spec b, table b, T, ess_perc_min, scheme)
+ * gives on a fresh wsmc_create(n, seeds[b]) context: final columns, log-weights, last ancestors,
+ * log evidence, per-step ESS trace, number of resamples, the last decision.
+ * specs: n_specs = 1 (one spec for every filter) or B; data: n_tables = 1 or B row-major tables of
+ * T x data_dim, back to back (may be NULL when data_dim == 0). With n_specs == B the specs must be
+ * of one shape (wsmc_ssm_spec_same_shape): only their numbers may differ.
+ * ctx gives the device and the stream; its particles, columns, weights, tape, counters and RNG
+ * position are neither read nor written, so the call may stand between any two statements of a
+ * program on ctx. Synchronous: on return every filter is complete.
+ * The call has the persistent route only. WSMC_EARG, with the reason in wsmc_last_error(): n above
+ * the cap for the spec's column count (wsmc_debug_ssm), multinomial or unknown resampling, more than
+ * WSMC_XPROG_MAX program instructions in the spec, a sharded or multi-device ctx, B < 1, T < 1,
+ * n < 1, n_specs or n_tables not 1 or B, null specs / seeds / out, null data with data_dim > 0,
+ * a spec wsmc_ssm_spec_check refuses ("spec b: ..."), specs of different shape. */
+int wsmc_ssm_run_batch(wsmc_ctx* ctx, const wsmc_ssm_spec* specs, int32_t n_specs,
+                       const double* data, int32_t n_tables, int32_t T, int32_t n, int32_t B,
+                       const uint64_t* seeds, double ess_perc_min, int32_t scheme,
+                       wsmc_ssm_batch_out* out);
+/* Host only: WSMC_OK when a and b differ in their numbers alone (an operand's c0 / coef, a dist's
+ * param, the value of a WSMC_X_CONST instruction); WSMC_EARG with the first differing field in
+ * wsmc_last_error() when a count, a column name, a kind, a column, a family, a data reference or
+ * an instruction's opcode (or a WSMC_X_POWI exponent) differs. */
+int wsmc_ssm_spec_same_shape(const wsmc_ssm_spec* a, const wsmc_ssm_spec* b);
+/* sizeof(wsmc_ssm_batch_out) as the library was built (layout check) */
+int wsmc_ssm_batch_out_sizeof(int64_t* bytes);
+/* segment_steps > 0 sets the steps per launch of wsmc_ssm_run_batch on this context, 0 restores the
+ * default (wsmc_ssm_run's, divided by the rounds of resident workgroups B takes), < 0 leaves it;
+ * stats_out[4] (may be NULL) = the last batch's resident workgroups per CU, the device's CU count,
+ * the segments it launched and its whole-call time in microseconds. */
+int wsmc_debug_ssm_batch(wsmc_ctx* ctx, int32_t segment_steps, int64_t* stats_out);
 /* per-kernel timing of the last fused run (HIP events on the ctx stream), ms */
 typedef struct {
     double total_ms;            /* whole run, first kernel to last                       */

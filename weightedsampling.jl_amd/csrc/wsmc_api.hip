@@ -5666,6 +5666,260 @@ int wsmc_debug_ssm(wsmc_ctx* c, int32_t segment_steps, int64_t* stats_out) {
     return WSMC_OK;
 }
 
+// ---- a batch of independent scalar-SSM runs (csrc/wsmc_ssm_batch.hip) ---------------------------
+// the first field in which two operands / statements / specs differ in shape, or empty
+static std::string ssm_operand_shape(const wsmc_operand& a, const wsmc_operand& b) {
+    for (int k = 0; k < 2; ++k) {
+        if (a.col[k] != b.col[k]) return "col[" + std::to_string(k) + "]";
+        if (a.comp[k] != b.comp[k]) return "comp[" + std::to_string(k) + "]";
+    }
+    return "";
+}
+static std::string ssm_stmt_shape(const wsmc_ssm_stmt& a, const wsmc_ssm_stmt& b) {
+    if (a.kind != b.kind) return "kind";
+    if (a.col != b.col) return "col";
+    if (a.kind == WSMC_SSM_SAMPLE || a.kind == WSMC_SSM_OBSERVE) {
+        if (a.dist.family != b.dist.family) return "dist.family";
+        if (a.dist.mean_fn != b.dist.mean_fn) return "dist.mean_fn";
+        if (a.dist.dim != b.dist.dim) return "dist.dim";
+        for (int k = 0; k < 4; ++k) {
+            const std::string w = ssm_operand_shape(a.dist.mu[k], b.dist.mu[k]);
+            if (!w.empty()) return "dist.mu[" + std::to_string(k) + "]." + w;
+        }
+        const std::string w = ssm_operand_shape(a.dist.scale, b.dist.scale);
+        if (!w.empty()) return "dist.scale." + w;
+    }
+    if (a.kind == WSMC_SSM_ASSIGN || a.kind == WSMC_SSM_OBSERVE) {
+        const std::string w = ssm_operand_shape(a.value, b.value);
+        if (!w.empty()) return "value." + w;
+    }
+    if (a.kind == WSMC_SSM_ASSIGN_EXPR) {
+        if (a.prog_len != b.prog_len) return "prog_len";
+        for (int q = 0; q < a.prog_len && q < WSMC_SSM_XPROG_MAX; ++q) {
+            const wsmc_xinst &x = a.prog[q], &y = b.prog[q];
+            const std::string at = "prog[" + std::to_string(q) + "].";
+            if (x.op != y.op) return at + "op";
+            if (x.op == WSMC_X_COL && x.col != y.col) return at + "col";
+            if (x.op == WSMC_X_COL && x.comp != y.comp) return at + "comp";
+            if (x.op == WSMC_X_POWI && std::memcmp(&x.c, &y.c, sizeof(double))) return at + "c (a WSMC_X_POWI exponent)";
+        }
+    }
+    return "";
+}
+static std::string ssm_spec_shape(const wsmc_ssm_spec* a, const wsmc_ssm_spec* b) {
+    if (a->n_cols != b->n_cols) return "n_cols";
+    if (a->data_dim != b->data_dim) return "data_dim";
+    if (a->n_init != b->n_init) return "n_init";
+    if (a->n_step != b->n_step) return "n_step";
+    for (int k = 0; k < a->n_cols && k < WSMC_SSM_MAX_COLS; ++k)
+        if (std::strncmp(a->col_names[k], b->col_names[k], WSMC_SSM_NAME_MAX)) return "col_names[" + std::to_string(k) + "]";
+    for (int q = 0; q < a->n_init && q < WSMC_SSM_MAX_INIT; ++q) {
+        const std::string w = ssm_stmt_shape(a->init[q], b->init[q]);
+        if (!w.empty()) return "init[" + std::to_string(q) + "]." + w;
+    }
+    for (int q = 0; q < a->n_step && q < WSMC_SSM_MAX_STMTS; ++q) {
+        const std::string w = ssm_stmt_shape(a->step[q], b->step[q]);
+        if (!w.empty()) return "step[" + std::to_string(q) + "]." + w;
+    }
+    return "";
+}
+
+int wsmc_ssm_spec_same_shape(const wsmc_ssm_spec* a, const wsmc_ssm_spec* b) {
+    if (!a || !b) return fail(WSMC_EARG, "null spec");
+    const std::string w = ssm_spec_shape(a, b);
+    if (!w.empty()) return fail(WSMC_EARG, "ssm specs differ in shape: " + w);
+    return WSMC_OK;
+}
+
+int wsmc_ssm_batch_out_sizeof(int64_t* bytes) {
+    if (!bytes) return fail(WSMC_EARG, "null argument");
+    *bytes = (int64_t)sizeof(wsmc_ssm_batch_out);
+    return WSMC_OK;
+}
+
+int wsmc_ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_specs, const double* data, int32_t n_tables,
+                       int32_t T, int32_t n, int32_t B, const uint64_t* seeds, double ess_min, int32_t scheme,
+                       wsmc_ssm_batch_out* out) {
+    // every refusal before any device call; the context's state is never read past its layout
+    if (!c) return fail(WSMC_EARG, "null context");
+    if (c->multi || is_sharded(c)) return fail(WSMC_EARG, "ssm batch: a sharded or multi-device context (one unsharded device runs a batch)");
+    if (B < 1) return fail(WSMC_EARG, "ssm batch: B < 1");
+    if (T < 1) return fail(WSMC_EARG, "ssm batch: T < 1");
+    if (n < 1) return fail(WSMC_EARG, "ssm batch: n < 1");
+    if (n_specs != 1 && n_specs != B) return fail(WSMC_EARG, "ssm batch: n_specs must be 1 or B");
+    if (n_tables != 1 && n_tables != B) return fail(WSMC_EARG, "ssm batch: n_tables must be 1 or B");
+    if (!seeds) return fail(WSMC_EARG, "ssm batch: null seeds");
+    if (!specs) return fail(WSMC_EARG, "ssm batch: null specs");
+    if (!out) return fail(WSMC_EARG, "ssm batch: null out");
+    for (int32_t b = 0; b < n_specs; ++b)
+        if (const char* w = ssm_spec_why(specs + b)) return fail(WSMC_EARG, "ssm batch: spec " + std::to_string(b) + ": " + w);
+    for (int32_t b = 1; b < n_specs; ++b) {
+        const std::string w = ssm_spec_shape(specs, specs + b);
+        if (!w.empty()) return fail(WSMC_EARG, "ssm batch: spec " + std::to_string(b) + " differs from spec 0 in shape: " + w);
+    }
+    const wsmc_ssm_spec* sp = specs;   // the batch's shape
+    const int S = sp->n_cols, dd = sp->data_dim;
+    if (dd > 0 && !data) return fail(WSMC_EARG, "ssm batch: null data for a spec that reads data");
+    if (!valid_scheme(scheme)) return fail(WSMC_EARG, "ssm batch: unknown resampling scheme");
+    if (scheme == WSMC_RESAMPLE_MULTINOMIAL)
+        return fail(WSMC_EARG, "ssm batch: multinomial resampling (the persistent workgroup has stratified and systematic)");
+    if (n > ssm_cap(S))
+        return fail(WSMC_EARG, "ssm batch: n = " + std::to_string(n) + " above the cap of " + std::to_string(ssm_cap(S)) + " particles for " +
+                                   std::to_string(S) + " columns");
+    int nprog = 0;
+    unsigned feat = 0;
+    for (int q = 0; q < sp->n_init + sp->n_step; ++q) {
+        const wsmc_ssm_stmt& s = q < sp->n_init ? sp->init[q] : sp->step[q - sp->n_init];
+        if (s.kind == WSMC_SSM_ASSIGN_EXPR) nprog += s.prog_len;
+        if (s.kind == WSMC_SSM_SAMPLE || s.kind == WSMC_SSM_OBSERVE) feat |= wsmc_dist_feat(&s.dist);
+    }
+    if (nprog > kSsmProgMax)
+        return fail(WSMC_EARG, "ssm batch: " + std::to_string(nprog) + " program instructions (more than " + std::to_string(kSsmProgMax) + ")");
+    using clk = std::chrono::steady_clock;
+    const auto t_in = clk::now();
+    WSMC_HIP(hipSetDevice(c->device));
+
+    // the images: ssm_dev_stmt per spec, so a filter's parameter bits are the single run's
+    std::vector<SsmBatchFilter> filt((size_t)B);
+    std::memset(filt.data(), 0, sizeof(SsmBatchFilter) * (size_t)B);
+    for (int32_t b = 0; b < B; ++b) {
+        const wsmc_ssm_spec* sb = specs + (n_specs == 1 ? 0 : b);
+        SsmBatchFilter& f = filt[(size_t)b];
+        if (b > 0 && n_specs == 1) {
+            f = filt[0];
+        } else {
+            int nins = 0;
+            for (int q = 0; q < sb->n_init; ++q) f.init[q] = ssm_dev_stmt(sb->init[q], f.ins, &nins);
+            for (int q = 0; q < sb->n_step; ++q) f.step[q] = ssm_dev_stmt(sb->step[q], f.ins, &nins);
+        }
+        f.seed = seeds[b];
+    }
+    // one allocation for the call: the state between segments ([B] rows of what a context keeps:
+    // zero columns, zero log-weights and a zero ancestors row are what wsmc_create and
+    // wsmc_col_create leave), the records, the images, the tables, the trace
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t nx = up(sizeof(double) * (size_t)B * S * n), nw = up(sizeof(double) * (size_t)B * n),
+                 nanc = up(sizeof(int32_t) * (size_t)B * n), nrec = up(sizeof(SsmBatchRec) * (size_t)B),
+                 nfilt = up(sizeof(SsmBatchFilter) * (size_t)B), ndata = up(sizeof(double) * (size_t)n_tables * T * dd),
+                 ntrace = out->ess_trace ? up(sizeof(double) * (size_t)B * T) : 0;
+    const size_t nstate = nx + nw + nanc + nrec;
+    struct Slab {
+        char* p = nullptr;
+        ~Slab() { if (p) (void)hipFree(p); }
+    } slab;
+    WSMC_HIP(hipMalloc(&slab.p, nstate + nfilt + ndata + ntrace + 256));
+    char* q = slab.p;
+    double* d_x = reinterpret_cast<double*>(q); q += nx;
+    double* d_w = reinterpret_cast<double*>(q); q += nw;
+    int32_t* d_anc = reinterpret_cast<int32_t*>(q); q += nanc;
+    SsmBatchRec* d_rec = reinterpret_cast<SsmBatchRec*>(q); q += nrec;
+    SsmBatchFilter* d_filt = reinterpret_cast<SsmBatchFilter*>(q); q += nfilt;
+    double* d_data = reinterpret_cast<double*>(q); q += ndata;
+    double* d_trace = ntrace ? reinterpret_cast<double*>(q) : nullptr;
+    for (int32_t b = 0; b < B; ++b)
+        filt[(size_t)b].data = dd > 0 ? d_data + (size_t)(n_tables == 1 ? 0 : b) * T * dd : nullptr;
+    hipStream_t st = c->stream;
+    // (from here an error leaves through the stream's end, so nothing is freed under a kernel)
+    auto run = [&]() -> hipError_t {
+        hipError_t e = hipMemsetAsync(slab.p, 0, nstate, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_filt, filt.data(), sizeof(SsmBatchFilter) * (size_t)B, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && dd > 0)
+            e = hipMemcpyAsync(d_data, data, sizeof(double) * (size_t)n_tables * T * dd, hipMemcpyHostToDevice, st);
+        return e;
+    };
+    hipError_t e = run();
+    SsmBatchArgs ka;
+    std::memset(&ka, 0, sizeof(ka));
+    ka.x = d_x;
+    ka.w = d_w;
+    ka.anc = d_anc;
+    ka.ess_trace = d_trace;
+    ka.rec = d_rec;
+    ka.filt = d_filt;
+    ka.N = n;
+    const int threads = ssm_threads(feat, n);
+    ka.P = (n + threads - 1) / threads;
+    ka.S = S;
+    ka.data_dim = dd;
+    ka.scheme = scheme;
+    ka.n_init = sp->n_init;
+    ka.n_step = sp->n_step;
+    ka.init_ops = ssm_op_count(sp->init, sp->n_init);
+    ka.step_ops = ssm_op_count(sp->step, sp->n_step);
+    ka.last_obs = ssm_last_observe(sp);
+    ka.T = T;
+    ka.B = B;
+    ka.ess_min = ess_min;
+    // steps a launch: the single run's, divided by the rounds of resident workgroups the batch
+    // takes, so a launch stays near the single run's 25 ms whatever B is
+    int per_cu = 0, cus = 0;
+    if (e == hipSuccess) e = ssm_batch_occupancy(c->device, feat, threads, ssm_lds_bytes(n, S), &per_cu, &cus);
+    if (e == hipSuccess && (per_cu < 1 || cus < 1)) e = hipErrorInvalidValue;
+    int64_t nseg = 0;
+    if (e == hipSuccess) {
+        const int64_t resident = (int64_t)per_cu * cus;
+        const int64_t rounds = ((int64_t)B + resident - 1) / resident;
+        const int32_t K1 = std::max(1, kSsmSegmentStmts / sp->n_step * 2 / std::max(2, (int)ka.P));
+        const int32_t K = c->ssm_batch_segment > 0 ? c->ssm_batch_segment : (int32_t)std::max<int64_t>(1, K1 / rounds);
+        for (int32_t t0 = 0; t0 < T && e == hipSuccess; t0 += K, ++nseg) {
+            ka.t0 = t0;
+            ka.nsteps = std::min<int32_t>(K, T - t0);
+            ka.first = t0 == 0;
+            ka.last = t0 + ka.nsteps == T;
+            e = launch_ssm_batch_segment(st, ka, feat, threads);
+        }
+    }
+    std::vector<SsmBatchRec> hrec((size_t)B);
+    auto down = [&](void* host, const void* dev, size_t bytes) {
+        if (e == hipSuccess && host) e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st);
+    };
+    down(hrec.data(), d_rec, sizeof(SsmBatchRec) * (size_t)B);
+    down(out->ess_trace, d_trace, sizeof(double) * (size_t)B * T);
+    down(out->cols, d_x, sizeof(double) * (size_t)B * S * n);
+    down(out->log_weights, d_w, sizeof(double) * (size_t)B * n);
+    down(out->last_ancestors, d_anc, sizeof(int32_t) * (size_t)B * n);
+    const hipError_t es = hipStreamSynchronize(st);   // also after an error: the slab is freed on return
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(WSMC_EHIP, std::string("ssm batch: ") + hipGetErrorString(e));
+    for (int32_t b = 0; b < B; ++b) {
+        const SsmBatchRec& r = hrec[(size_t)b];
+        if (out->log_evidence) {   // wsmc_log_evidence's: one shard's record
+            wsmc_shard_stats s1;
+            s1.M = r.M;
+            s1.Q = r.Q;
+            s1.Q2 = r.Q2;
+            s1.Wf = r.Wf;
+            s1.Wf2 = r.Wf2;
+            s1.n = (uint64_t)n;
+            out->log_evidence[b] = wsmc_global_log_evidence(&s1, 1);
+        }
+        if (out->n_resamples) out->n_resamples[b] = r.nres;
+        if (out->last_resampled) out->last_resampled[b] = r.last_dec;
+    }
+    c->ssm_batch_per_cu = per_cu;
+    c->ssm_batch_cus = cus;
+    c->ssm_batch_segments = nseg;
+    c->ssm_batch_wall_us = (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(clk::now() - t_in).count();
+    return WSMC_OK;
+}
+
+int wsmc_debug_ssm_batch(wsmc_ctx* c, int32_t segment_steps, int64_t* stats_out) {
+    if (!c) return fail(WSMC_EARG, "null context");
+    if (c->multi) return fail(WSMC_EARG, "ssm batch: a multi-device context");
+    if (segment_steps >= 0) c->ssm_batch_segment = segment_steps;
+    if (stats_out) {
+        if (!c->ssm_batch_cus) {   // before the first batch: the device's count all the same
+            int cus = 0;
+            if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess) c->ssm_batch_cus = cus;
+        }
+        stats_out[0] = c->ssm_batch_per_cu;
+        stats_out[1] = c->ssm_batch_cus;
+        stats_out[2] = c->ssm_batch_segments;
+        stats_out[3] = c->ssm_batch_wall_us;
+    }
+    return WSMC_OK;
+}
+
 }  // extern "C"
 
 int wsmc_debug_jit_stats(int64_t* stats_out) {

@@ -383,6 +383,10 @@ struct wsmc_ctx {
     int32_t ssm_segment = 0;                // steps per launch (0: kSsmSegmentStmts / the step's statements)
     int64_t ssm_runs = 0, ssm_stmt_runs = 0, ssm_segments = 0;   // cumulative (wsmc_debug_ssm)
     int64_t ssm_book_us = 0, ssm_wall_us = 0;
+    // wsmc_ssm_run_batch (it touches nothing else of the context): steps per launch (0: the
+    // default), then the last call's resident blocks per CU, CU count, segments and wall time
+    int32_t ssm_batch_segment = 0;
+    int64_t ssm_batch_per_cu = 0, ssm_batch_cus = 0, ssm_batch_segments = 0, ssm_batch_wall_us = 0;
     bool timing = false;
     std::vector<hipEvent_t> events;
     wsmc_run_timing last_timing{};
@@ -963,6 +967,44 @@ size_t ssm_lds_bytes(int n, int S);
 // feat: WSMC_FEAT_EXT / WSMC_FEAT_GAM bits over the spec's dists (the kernel's instantiation)
 int ssm_threads(unsigned feat, int n);
 hipError_t launch_ssm_segment(hipStream_t s, const SsmArgs& a, unsigned feat, int threads);
+// B independent runs of that kernel's step body in one launch, one workgroup a filter
+// (csrc/wsmc_ssm_batch.hip, wsmc_ssm_run_batch). The statements' shape is one for the batch, their
+// numbers are not, so each filter reads its own image of the compact statements from device
+// memory (block-uniform address: scalar loads), with its seed and its data table.
+struct SsmBatchFilter {
+    SsmStmt init[WSMC_SSM_MAX_INIT];
+    SsmStmt step[WSMC_SSM_MAX_STMTS];
+    SsmIns ins[kSsmProgMax];
+    uint64_t seed;
+    const double* data;       // [T x data_dim] this filter's table (shared tables: one pointer B times)
+};
+struct SsmBatchRec {          // filter b's LgRecord, and the record of its final weights
+    long long nres;
+    int32_t last_dec, pad;
+    double last_ess;
+    double M;                 // written by the run's last segment: wsmc_shard_stats of the weights
+    unsigned long long Q, Q2, Wf, Wf2;
+};
+struct SsmBatchArgs {
+    double* x;                // [B][S][N] the columns (read unless `first`, written at the segment's end)
+    double* w;                // [B][N] log-weights
+    int32_t* anc;             // [B][N] row b written when a step of the segment resampled
+    double* ess_trace;        // [B][T] or null
+    SsmBatchRec* rec;         // [B]
+    const SsmBatchFilter* filt;   // [B]
+    int32_t N, P;             // particles, particles per thread
+    int32_t S, data_dim;
+    int32_t t0, nsteps;       // the segment's steps [t0, t0 + nsteps)
+    int32_t first, last;      // the run's first segment (it runs `init`) / last one (it takes the record)
+    int32_t n_init, n_step;
+    int32_t init_ops, step_ops;
+    int32_t last_obs, scheme;
+    int32_t T, B;
+    double ess_min;
+};
+// blocks of the variant that are resident on one CU (by registers, waves and LDS), and the device's CUs
+hipError_t ssm_batch_occupancy(int device, unsigned feat, int threads, size_t lds, int* per_cu, int* cus);
+hipError_t launch_ssm_batch_segment(hipStream_t s, const SsmBatchArgs& a, unsigned feat, int threads);
 // one handle over several devices (wsmc_multi.hip): the ABI entry points fan out
 int multi_destroy(wsmc_ctx* c);
 wsmc_ctx* multi_first(wsmc_ctx* c);

@@ -1,0 +1,216 @@
+// wsmc_ssm_batch.hip — B independent fused runs of a specified scalar SSM in one launch
+// (wsmc_ssm_run_batch): block b of a dim3(B) grid is csrc/wsmc_ssm.hip's persistent workgroup for
+// filter b, with the same step body (csrc/wsmc_ssm_body.h), the same LDS layout and the same
+// thread-to-particle map, so filter b's bits are those of wsmc_ssm_run on a fresh context.
+//
+// What differs per filter is read per block: its image of the compact statements (the numbers
+// differ, the shape does not), its seed and its data table, from filt[blockIdx.x] through a
+// constant-address-space pointer. The images are written before the first launch and by nothing
+// while a kernel runs; the address is block-uniform, so the loads are scalar and the branches
+// uniform, as with the single run's kernel arguments. What is one for the batch (sizes, the
+// segment, the scheme, the threshold) rides in the kernel arguments.
+//
+// No block waits on another: a grid larger than the device holds simply queues. The state between
+// segments is in the call's device buffers, [B] rows of what the single run keeps in its context.
+// The run's last segment leaves the record of the final weights (the max and the exact integer
+// sums the Resample takes), from which the host finishes the evidence.
+#ifdef __HIP_DEVICE_COMPILE__
+#define WSMC_TABLES_LDS   // include/wsmc_math.h: the device pass reads LDS copies of the tables
+#endif
+#include "wsmc_ssm_body.h"
+
+namespace wsmc {
+
+namespace {
+typedef const SsmBatchFilter __attribute__((address_space(4))) * SsFilterPtr;
+}
+
+template <unsigned FEAT, int THREADS>
+__global__ __launch_bounds__(THREADS) void k_ssm_batch_segment(const SsmBatchArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char ssb_smem[];
+    const int tid = (int)threadIdx.x, nthr = (int)blockDim.x;
+    const size_t b = blockIdx.x;
+    const SsmBatchFilter& f = *(const SsmBatchFilter*)((SsFilterPtr)a.filt + b);
+    const int N = a.N, P = a.P, S = a.S;
+    SsState L;
+    L.stride = (int)ss_n8(N);
+    L.cb = reinterpret_cast<double*>(ssb_smem);
+    L.lw = L.cb + (size_t)(S + 1) * L.stride;
+    L.anc = reinterpret_cast<int32_t*>(L.lw + L.stride);
+    L.red = reinterpret_cast<uint64_t*>(L.anc + ss_n4(N));
+    L.S = S;
+    L.off = 0;
+    L.N = N;
+    L.i0 = tid * P < N ? tid * P : N;
+    L.i1 = L.i0 + P < N ? L.i0 + P : N;
+    L.lane = tid & 63;
+    L.wave = tid >> 6;
+    L.nw = (nthr + 63) >> 6;
+
+    double* gw = a.w + b * (size_t)N;
+    double* gx = a.x + b * (size_t)S * (size_t)N;
+    int32_t* ganc = a.anc + b * (size_t)N;
+    SsmBatchRec* rec = a.rec + b;
+
+#ifdef WSMC_TABLES_LDS
+    wsmc_tables_to_lds();   // before any log / exp (every thread: it ends in a barrier)
+#endif
+    for (int i = L.i0; i < L.i1; ++i) L.lw[i] = gw[i];
+    for (int k = 0; k < S; ++k) {
+        const double* src = gx + (size_t)k * N;
+        double* dst = L.cb + (size_t)k * L.stride;
+        for (int i = L.i0; i < L.i1; ++i) dst[i] = src[i];
+    }
+
+    const int K = wsmc_qbits((uint64_t)N);
+    const int dd = a.data_dim;
+    const SsConstPtr data = (SsConstPtr)f.data;
+    const uint64_t seed = f.seed;
+    long long nres = 0;
+    int last_dec = 0, ran = 0;
+    double last_ess = 0.0;
+    SsData dv = {0.0, 0.0, 0.0, 0.0};
+
+    SsData dnext = dv;
+    if (a.nsteps > 0) dnext = ss_row(data, dd, a.t0);
+
+    // k_ssm_segment's loop: s = -1 is `init` (a fresh context: the op counter starts at 0)
+    static_assert(offsetof(SsmBatchFilter, step) == offsetof(SsmBatchFilter, init) + WSMC_SSM_MAX_INIT * sizeof(SsmStmt),
+                  "step follows init: one statement array");
+    for (int s = a.first ? -1 : 0; s < a.nsteps; ++s) {
+        const int t = a.t0 + s;
+        const bool init = s < 0;
+        const SsmStmt* list = f.init + (init ? 0 : WSMC_SSM_MAX_INIT);
+        const int nst = init ? a.n_init : a.n_step;
+        uint64_t op = init ? 0 : (uint64_t)a.init_ops + (uint64_t)a.step_ops * (uint64_t)t;
+        if (!init) {
+            dv = dnext;
+            if (s + 1 < a.nsteps) dnext = ss_row(data, dd, t + 1);   // in flight during this step
+        }
+        for (int q = 0; q < nst; ++q) {
+            const SsmStmt& st = list[q];
+            ss_statement<FEAT>(st, f.ins, L, dv, seed, op);
+            if (st.kind == WSMC_SSM_SAMPLE) {
+                op += 2;   // the draws, then a Resample that does not run (the weights have not changed)
+            } else if (st.kind == WSMC_SSM_OBSERVE) {
+                const SsDecision d = ss_resample(L, K, a.ess_min, a.scheme, seed, op);
+                op += 1;
+                nres += d.resampled;
+                last_dec = d.resampled;
+                last_ess = d.ess;
+                ran = 1;
+                if (!init && q == a.last_obs && a.ess_trace && tid == 0) a.ess_trace[b * (size_t)a.T + t] = d.ess;
+            }
+        }
+    }
+
+    for (int k = 0; k < S; ++k) {
+        double* dst = gx + (size_t)k * N;
+        const double* src = L.cb + (size_t)ss_buf(L, k) * L.stride;
+        for (int i = L.i0; i < L.i1; ++i) dst[i] = src[i];
+    }
+    for (int i = L.i0; i < L.i1; ++i) gw[i] = L.lw[i];
+    if (nres > 0)
+        for (int i = L.i0; i < L.i1; ++i) ganc[i] = L.anc[i];
+    if (tid == 0 && ran) {
+        rec->nres += nres;
+        rec->last_dec = last_dec;
+        rec->last_ess = last_ess;
+    }
+
+    // the run's end: the record of the final weights, ss_resample's max and sums (exact integers:
+    // any order of summation gives the same record), for wsmc_global_log_evidence on the host
+    if (a.last) {
+        uint64_t* red0 = L.red;
+        uint64_t* red1 = L.red + kSsWaves * 4;
+        __syncthreads();   // the last Resample's readers of the scratch are through
+        uint64_t menc = WSMC_ORD_NEG_INF;
+        for (int i = L.i0; i < L.i1; ++i) {
+            const uint64_t e = wsmc_ord_enc(L.lw[i]);
+            menc = e > menc ? e : menc;
+        }
+        for (int m = 32; m >= 1; m >>= 1) {
+            const uint64_t o = ss_shfl_xor(menc, m);
+            menc = o > menc ? o : menc;
+        }
+        if (L.lane == 0) red0[L.wave] = menc;
+        __syncthreads();
+        for (int w = 0; w < L.nw; ++w) menc = red0[w] > menc ? red0[w] : menc;
+        const double M = wsmc_ord_dec(menc);
+        const double R = wsmc_qref(M);
+        uint64_t sQ = 0, sQ2 = 0, sWf = 0, sWf2 = 0;
+        for (int i = L.i0; i < L.i1; ++i) {
+            const wsmc_qparts p = wsmc_qparts_of(L.lw[i], R, K);
+            sQ += p.q; sQ2 += p.q2; sWf += p.wf; sWf2 += p.wf2;
+        }
+        for (int m = 32; m >= 1; m >>= 1) {
+            sQ += ss_shfl_xor(sQ, m);
+            sQ2 += ss_shfl_xor(sQ2, m);
+            sWf += ss_shfl_xor(sWf, m);
+            sWf2 += ss_shfl_xor(sWf2, m);
+        }
+        if (L.lane == 0) {
+            red1[L.wave * 4 + 0] = sQ; red1[L.wave * 4 + 1] = sQ2; red1[L.wave * 4 + 2] = sWf; red1[L.wave * 4 + 3] = sWf2;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            uint64_t Q = 0, Q2 = 0, Wf = 0, Wf2 = 0;
+            for (int w = 0; w < L.nw; ++w) {
+                Q += red1[w * 4 + 0]; Q2 += red1[w * 4 + 1];
+                Wf += red1[w * 4 + 2]; Wf2 += red1[w * 4 + 3];
+            }
+            rec->M = M;
+            rec->Q = Q; rec->Q2 = Q2; rec->Wf = Wf; rec->Wf2 = Wf2;
+        }
+    }
+}
+
+namespace {
+
+template <unsigned FEAT, int THREADS>
+hipError_t ssb_occupancy(int threads, size_t lds, int* per_cu) {
+    const void* k = reinterpret_cast<const void*>(k_ssm_batch_segment<FEAT, THREADS>);
+    if (lds > 65536 - 4096) {   // the occupancy query refuses dynamic LDS the kernel has not asked for
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k, threads, lds);
+}
+
+template <unsigned FEAT, int THREADS>
+hipError_t ssb_launch(hipStream_t s, const SsmBatchArgs& a, int threads, size_t lds) {
+    if (lds > 65536 - 4096) {   // past 64 KiB a kernel must ask for its dynamic LDS (per device: set at each launch)
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ssm_batch_segment<FEAT, THREADS>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((k_ssm_batch_segment<FEAT, THREADS>), dim3((unsigned)a.B), dim3(threads), lds, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t ssm_batch_occupancy(int device, unsigned feat, int threads, size_t lds, int* per_cu, int* cus) {
+    hipError_t e = hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, device);
+    if (e != hipSuccess) return e;
+    if (feat & WSMC_FEAT_GAM) e = ssb_occupancy<kSsFeatGam, kSsGamThreads>(threads, lds, per_cu);
+    else if (feat & WSMC_FEAT_EXT) e = ssb_occupancy<kSsFeatExt, kSsMaxThreads>(threads, lds, per_cu);
+    else e = ssb_occupancy<0u, kSsMaxThreads>(threads, lds, per_cu);
+    return e;
+}
+
+hipError_t launch_ssm_batch_segment(hipStream_t s, const SsmBatchArgs& a, unsigned feat, int threads) {
+    const int tmax = (feat & WSMC_FEAT_GAM) ? kSsGamThreads : kSsMaxThreads;
+    if (a.B < 1 || a.S < 1 || a.S > WSMC_SSM_MAX_COLS || a.N < 1 || a.N > ssm_cap(a.S) || threads < 64 || threads > tmax ||
+        (threads & 63) || (int64_t)a.P * threads < a.N || a.nsteps < 0 || a.t0 < 0 || a.t0 + a.nsteps > a.T ||
+        a.data_dim < 0 || a.data_dim > WSMC_SSM_MAX_DATA || a.n_init < 0 || a.n_init > WSMC_SSM_MAX_INIT || a.n_step < 1 ||
+        a.n_step > WSMC_SSM_MAX_STMTS || !a.x || !a.w || !a.anc || !a.rec || !a.filt)
+        return hipErrorInvalidValue;
+    const size_t lds = ssm_lds_bytes(a.N, a.S);
+    if (lds + 4096 > 160 * 1024) return hipErrorInvalidValue;   // with the static tables: the workgroup's LDS
+    if (feat & WSMC_FEAT_GAM) return ssb_launch<kSsFeatGam, kSsGamThreads>(s, a, threads, lds);
+    if (feat & WSMC_FEAT_EXT) return ssb_launch<kSsFeatExt, kSsMaxThreads>(s, a, threads, lds);
+    return ssb_launch<0u, kSsMaxThreads>(s, a, threads, lds);
+}
+
+}  // namespace wsmc

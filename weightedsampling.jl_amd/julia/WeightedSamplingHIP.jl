@@ -839,4 +839,65 @@ function ssm_run!(state::HipState, spec::WsmcSsmSpec, data::AbstractVecOrMat; sc
     return ess_trace ? (ev[], tr) : ev[]
 end
 
+# wsmc_ssm_batch_out (include/wsmc.h): host buffers of a batch's results, C_NULL for the ones not wanted
+struct WsmcSsmBatchOut
+    log_evidence::Ptr{Float64}
+    ess_trace::Ptr{Float64}
+    cols::Ptr{Float64}
+    log_weights::Ptr{Float64}
+    last_ancestors::Ptr{Int32}
+    n_resamples::Ptr{Int64}
+    last_resampled::Ptr{Int32}
+end
+
+"""
+    ssm_same_shape(a, b) -> Bool
+
+`wsmc_ssm_spec_same_shape` (host only): the two specs differ in their numbers alone, so one batch
+may hold both.
+"""
+ssm_same_shape(a::WsmcSsmSpec, b::WsmcSsmSpec) =
+    ccall((:wsmc_ssm_spec_same_shape, libwsmc), Cint, (Ref{WsmcSsmSpec}, Ref{WsmcSsmSpec}), a, b) == 0
+
+"""
+    ssm_run_batch(state, specs, data, n, seeds; scheme, ess_trace=false, keep_state=false)
+
+B = length(seeds) independent filters of `n` particles in one call (`wsmc_ssm_run_batch`), one
+persistent workgroup each; filter b is `ssm_run!` of spec b on a fresh state of seed `seeds[b]`.
+`specs` is one spec or a vector of B of one shape; `data` one table (a vector or T x data_dim) or a
+vector of B tables. `state` gives the device and the stream and is not changed. Returns a named
+tuple: `log_evidence`, `n_resamples`, `last_resampled`, and `ess` (T x B), `cols` (n x n_cols x B),
+`log_weights`, `last_ancestors` (n x B) when asked for. (Written against the C ABI; not run in
+this repository's checks, which have no Julia.)
+"""
+function ssm_run_batch(state::HipState, specs, data, n::Integer, seeds::AbstractVector{<:Integer};
+                       scheme=RESAMPLE_STRATIFIED, ess_trace=false, keep_state=false)
+    B = length(seeds)
+    sp = specs isa WsmcSsmSpec ? [specs] : collect(WsmcSsmSpec, specs)
+    tabs = data isa AbstractVector{<:AbstractVecOrMat} ? collect(data) : [data]
+    length(sp) in (1, B) && length(tabs) in (1, B) || throw(ArgumentError("one spec / table, or one per filter"))
+    T = size(tabs[1], 1)
+    all(t -> size(t, 1) == T, tabs) || throw(ArgumentError("the filters' tables must have one length"))
+    rowmajor(t) = Vector{Float64}(vec(permutedims(reshape(Float64.(t), T, :))))
+    d = reduce(vcat, rowmajor.(tabs))
+    S = Int(sp[1].n_cols)
+    ev = Vector{Float64}(undef, B); nres = Vector{Int64}(undef, B); last = Vector{Int32}(undef, B)
+    tr = ess_trace ? Matrix{Float64}(undef, T, B) : nothing
+    cols = keep_state ? Array{Float64}(undef, n, S, B) : nothing
+    lw = keep_state ? Matrix{Float64}(undef, n, B) : nothing
+    anc = keep_state ? Matrix{Int32}(undef, n, B) : nothing
+    sd = Vector{UInt64}(seeds .% UInt64)
+    GC.@preserve ev nres last tr cols lw anc begin
+        p(a) = a === nothing ? C_NULL : pointer(a)
+        out = WsmcSsmBatchOut(pointer(ev), p(tr), p(cols), p(lw), p(anc), pointer(nres), pointer(last))
+        check(ccall((:wsmc_ssm_run_batch, libwsmc), Cint,
+                    (Ptr{Cvoid}, Ptr{WsmcSsmSpec}, Int32, Ptr{Float64}, Int32, Int32, Int32, Int32, Ptr{UInt64},
+                     Float64, Int32, Ref{WsmcSsmBatchOut}),
+                    state.store.ctx, sp, length(sp), isempty(d) ? C_NULL : d, length(tabs), T, n, B, sd,
+                    state.ess_perc_min, scheme, out))
+    end
+    return (log_evidence=ev, n_resamples=nres, last_resampled=last .!= 0, ess=tr, cols=cols, log_weights=lw,
+            last_ancestors=anc)
+end
+
 end # module

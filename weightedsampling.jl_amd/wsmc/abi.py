@@ -111,6 +111,14 @@ class SsmSpec(C.Structure):
                 ("init", SsmStmt * SSM_MAX_INIT), ("step", SsmStmt * SSM_MAX_STMTS)]
 
 
+class SsmBatchOut(C.Structure):
+    """wsmc_ssm_batch_out: caller-owned host buffers of wsmc_ssm_run_batch's results (NULL: not wanted)"""
+    _fields_ = [("log_evidence", C.POINTER(C.c_double)), ("ess_trace", C.POINTER(C.c_double)),
+                ("cols", C.POINTER(C.c_double)), ("log_weights", C.POINTER(C.c_double)),
+                ("last_ancestors", C.POINTER(C.c_int32)), ("n_resamples", C.POINTER(C.c_int64)),
+                ("last_resampled", C.POINTER(C.c_int32))]
+
+
 class RunTiming(C.Structure):
     _fields_ = [("total_ms", C.c_double), ("propagate_ms", C.c_double),
                 ("reduce_ms", C.c_double), ("resample_ms", C.c_double),
@@ -185,6 +193,11 @@ SIGNATURES = {
     "wsmc_ssm_spec_sizeof": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "wsmc_ssm_run": (C.c_int, [_P, C.POINTER(SsmSpec), _D, C.c_int32, C.c_double, C.c_int32, _D, _D]),
     "wsmc_debug_ssm": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int64)]),
+    "wsmc_ssm_run_batch": (C.c_int, [_P, C.POINTER(SsmSpec), C.c_int32, _D, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.POINTER(C.c_uint64), C.c_double, C.c_int32, C.POINTER(SsmBatchOut)]),
+    "wsmc_ssm_spec_same_shape": (C.c_int, [C.POINTER(SsmSpec), C.POINTER(SsmSpec)]),
+    "wsmc_ssm_batch_out_sizeof": (C.c_int, [C.POINTER(C.c_int64)]),
+    "wsmc_debug_ssm_batch": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int64)]),
     "wsmc_run_set_timing": (C.c_int, [_P, C.c_int32]),
     "wsmc_run_get_timing": (C.c_int, [_P, C.POINTER(RunTiming)]),
     "wsmc_debug_kernel_bench": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _D]),

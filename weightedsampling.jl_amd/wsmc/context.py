@@ -15,6 +15,7 @@ import numpy as np
 
 from . import abi
 from .abi import Dist, Operand, RunTiming, State, check, load_library
+from .ssm import batch_arguments
 
 _D = C.POINTER(C.c_double)
 _I32P = C.POINTER(C.c_int32)
@@ -30,6 +31,13 @@ def _operands4(exprs) -> C.Array:
     for k in range(4):
         arr[k] = ops[k] if k < len(ops) else ops[0]
     return arr
+
+
+class SsmBatchResult:
+    """What Context.ssm_run_batch returns: [B] arrays log_evidence, n_resamples, last_resampled;
+    ess [B, T] when the trace was asked for; cols (name -> [B, n]), log_weights and last_ancestors
+    [B, n] when the state was (None otherwise)."""
+    log_evidence = n_resamples = last_resampled = ess = cols = log_weights = last_ancestors = None
 
 
 class Context:
@@ -487,6 +495,63 @@ class Context:
         if steps < 0:
             raise ValueError("steps must be >= 0")
         check(self._L.wsmc_debug_ssm(self._h, int(steps), None))
+
+    def ssm_run_batch(self, specs, data, n: int, seeds, ess_perc_min=1.0, scheme: int = abi.RESAMPLE_STRATIFIED,
+                      ess_trace: bool = False, state: bool = False, T: int | None = None) -> "SsmBatchResult":
+        """B = len(seeds) independent filters of n particles in one call (wsmc_ssm_run_batch), one
+        persistent workgroup each: filter b is, bit for bit, ssm_run(spec b, table b) on a fresh
+        Context(n, seed=seeds[b]). This context gives the device and the stream; its own particles
+        and state are not touched.
+        specs: one wsmc.SSM, or a list of B of one shape (SSM.same_shape: only numbers differ).
+        data: one table (T values or T rows), or a list / 3-D array of B tables of one length.
+        Returns an SsmBatchResult: log_evidence, n_resamples, last_resampled ([B] each), with
+        ess_trace `ess` [B, T], with state `cols` (name -> [B, n]), `log_weights` [B, n] and
+        `last_ancestors` [B, n] (row b is zeros while filter b has not resampled)."""
+        spec_list, tabs, seeds_a = batch_arguments(specs, data, n, seeds, T)   # (before any device call)
+        B, first, steps = len(seeds_a), spec_list[0], len(tabs[0])
+        tab = np.ascontiguousarray(np.stack(tabs)) if tabs[0].size else None
+        arr = (abi.SsmSpec * len(spec_list))()
+        for k, s in enumerate(spec_list):
+            C.memmove(C.byref(arr[k]), C.byref(s.spec), C.sizeof(abi.SsmSpec))
+        S = len(first.cols)
+        res = SsmBatchResult()
+        res.log_evidence = np.empty(B)
+        res.n_resamples = np.empty(B, dtype=np.int64)
+        res.last_resampled = np.empty(B, dtype=np.int32)
+        out = abi.SsmBatchOut()
+        out.log_evidence = _dptr(res.log_evidence)
+        out.n_resamples = res.n_resamples.ctypes.data_as(C.POINTER(C.c_int64))
+        out.last_resampled = res.last_resampled.ctypes.data_as(_I32P)
+        if ess_trace:
+            res.ess = np.empty((B, steps))
+            out.ess_trace = _dptr(res.ess)
+        if state:
+            cols = np.empty((B, S, int(n)))
+            res.log_weights = np.empty((B, int(n)))
+            res.last_ancestors = np.empty((B, int(n)), dtype=np.int32)
+            out.cols = _dptr(cols)
+            out.log_weights = _dptr(res.log_weights)
+            out.last_ancestors = res.last_ancestors.ctypes.data_as(_I32P)
+        check(self._L.wsmc_ssm_run_batch(self._h, arr, len(spec_list), _dptr(tab) if tab is not None else None, len(tabs),
+                                         steps, int(n), B, seeds_a.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                         float(ess_perc_min), int(scheme), C.byref(out)))
+        res.last_resampled = res.last_resampled.astype(bool)
+        if state:
+            res.cols = {name: cols[:, k, :] for k, name in enumerate(first.cols)}
+        return res
+
+    def ssm_batch_stats(self) -> dict:
+        """wsmc_debug_ssm_batch's figures: the last batch's resident workgroups per CU, the device's
+        CU count (known before the first batch), the segments it launched and its whole-call seconds."""
+        st = (C.c_int64 * 4)()
+        check(self._L.wsmc_debug_ssm_batch(self._h, -1, st))
+        return {"blocks_per_cu": int(st[0]), "cus": int(st[1]), "segments": int(st[2]), "call_s": st[3] / 1e6}
+
+    def set_ssm_batch_segment(self, steps: int) -> None:
+        """Steps per launch of ssm_run_batch on this context (0 restores the default)."""
+        if steps < 0:
+            raise ValueError("steps must be >= 0")
+        check(self._L.wsmc_debug_ssm_batch(self._h, int(steps), None))
 
     def set_timing(self, enabled: bool) -> None:
         check(self._L.wsmc_run_set_timing(self._h, int(bool(enabled))))

@@ -49,6 +49,33 @@ def _general(rhs) -> bool:
     return isinstance(rhs, Fx) or (isinstance(rhs, Expr) and rhs.fx is not None)
 
 
+def batch_arguments(specs, data, n, seeds, T=None):
+    """Context.ssm_run_batch's arguments, checked on the host alone: (the specs as a list of 1 or
+    B, the tables as a list of 1 or B arrays of one shape, the seeds as B uint64). ValueError names
+    the argument whose length fits neither 1 nor B = len(seeds)."""
+    seeds_a = np.ascontiguousarray(np.asarray([int(s) & (2**64 - 1) for s in seeds], dtype=np.uint64))
+    B = len(seeds_a)
+    if B < 1:
+        raise ValueError("seeds: at least one filter")
+    if int(n) < 1:
+        raise ValueError("n: at least one particle")
+    spec_list = list(specs) if isinstance(specs, (list, tuple)) else [specs]
+    if len(spec_list) not in (1, B):
+        raise ValueError(f"specs: one spec or one per filter ({B}), got {len(spec_list)}")
+    first = spec_list[0]
+    # B tables: a 3-D array, or a list of arrays (a list of numbers or of rows is one table)
+    many = isinstance(data, np.ndarray) and data.ndim == 3
+    many = many or (isinstance(data, (list, tuple)) and len(data) > 0 and all(isinstance(d, np.ndarray) for d in data))
+    tabs = [first.table(d, T) for d in data] if many else [first.table(data, T)]
+    if len(tabs) not in (1, B):
+        raise ValueError(f"data: one table or one per filter ({B}), got {len(tabs)}")
+    if any(t.shape != tabs[0].shape for t in tabs):
+        raise ValueError("data: the filters' tables must have one length")
+    if len(tabs[0]) < 1:
+        raise ValueError("data: at least one step")
+    return spec_list, tabs, seeds_a
+
+
 class SSM:
     """A builder for wsmc_ssm_spec: SSM(cols=[...]).init(...).step(...)."""
 
@@ -150,6 +177,20 @@ class SSM:
     def check(self) -> None:
         """wsmc_ssm_spec_check (host only): raises WSMCError(WSMC_EARG) with the reason"""
         abi.check(abi.load_library().wsmc_ssm_spec_check(C.byref(self.spec)))
+
+    def shape_difference(self, other: "SSM") -> str | None:
+        """wsmc_ssm_spec_same_shape (host only): None when the two specs differ in their numbers
+        alone (what one batch of Context.ssm_run_batch may hold), else the library's message, which
+        names the first differing field"""
+        L = abi.load_library()
+        if L.wsmc_ssm_spec_same_shape(C.byref(self.spec), C.byref(other.spec)) == abi.WSMC_OK:
+            return None
+        return L.wsmc_last_error().decode()
+
+    def same_shape(self, other: "SSM") -> bool:
+        """True when `other` differs from this spec in its numbers alone: operand constants and
+        coefficients, dist parameters, program constants (shape_difference says where it does not)"""
+        return self.shape_difference(other) is None
 
     def table(self, data, T: int | None = None) -> np.ndarray:
         """the run's data as the T x data_dim table the C entry point takes (a spec that reads no
