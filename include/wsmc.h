@@ -549,6 +549,41 @@ int wsmc_ssm_batch_out_sizeof(int64_t* bytes);
  * stats_out[4] (may be NULL) = the last batch's resident workgroups per CU, the device's CU count,
  * the segments it launched and its whole-call time in microseconds. */
 int wsmc_debug_ssm_batch(wsmc_ctx* ctx, int32_t segment_steps, int64_t* stats_out);
+/* ---- the per-step filtering trace of the two runs above ------------------------------------
+ * Trace point t (t = 0 .. T-1) is the ESS trace's: after step t's last OBSERVE, before the
+ * Resample that follows it. Row t is what the operators return there when the statements are
+ * issued one by one: mean[t][k] and var[t][k] are mean[k] and cov[k * d + k] of
+ * wsmc_weighted_moments with d = n_cols and expression k = column k alone (c0 = 0, coef = 1), so
+ * E[x_t | y_1:t] and the uncorrected variance under exp_norm of the weights; log_evidence[t] is
+ * wsmc_log_evidence (cumulative: its first difference is log p(y_t | y_1:t-1)); ess[t] is the
+ * ESS trace. Bit for bit, NaN kept. A function of the state is traced by making it a column.
+ * Caller-owned host buffers, each may be NULL (not wanted). */
+typedef struct {
+    double* ess;                /* [T]          (batch: [B][T])         */
+    double* mean;               /* [T][n_cols]  (batch: [B][T][n_cols]), the spec's column order */
+    double* var;                /* [T][n_cols]  (batch: [B][T][n_cols]) */
+    double* log_evidence;       /* [T]          (batch: [B][T])         */
+} wsmc_ssm_trace;
+/* sizeof(wsmc_ssm_trace) as the library was built (layout check) */
+int wsmc_ssm_trace_sizeof(int64_t* bytes);
+/* wsmc_ssm_run with the trace. Everything else the run leaves (columns, weights, ancestors, state
+ * fields, tape, evidence, RNG positions, wsmc_debug_ssm's routes) is bit for bit the untraced
+ * run's, and neither the route nor the particle caps depend on the trace. On the persistent
+ * route the workgroup takes the moments from LDS in the canonical order of summation; on the
+ * statement route the library calls wsmc_weighted_moments and wsmc_log_evidence at the trace
+ * point, where the Resample waits as it does for the ESS trace. trace NULL, or every member NULL:
+ * wsmc_ssm_run without an ESS trace. */
+int wsmc_ssm_run_traced(wsmc_ctx* ctx, const wsmc_ssm_spec* spec, const double* data, int32_t T,
+                        double ess_perc_min, int32_t scheme, double* log_evidence_out,
+                        const wsmc_ssm_trace* trace);
+/* wsmc_ssm_run_batch with the trace of every filter (row b of each array is filter b's, what
+ * wsmc_ssm_run_traced gives on a fresh wsmc_create(n, seeds[b]) context); the same refusals. The
+ * ESS trace goes to out->ess_trace and trace->ess, whichever is set. The trace is part of the
+ * call's device allocation: 8 B T (2 n_cols + 2) bytes when all four are asked for. */
+int wsmc_ssm_run_batch_traced(wsmc_ctx* ctx, const wsmc_ssm_spec* specs, int32_t n_specs,
+                              const double* data, int32_t n_tables, int32_t T, int32_t n, int32_t B,
+                              const uint64_t* seeds, double ess_perc_min, int32_t scheme,
+                              wsmc_ssm_batch_out* out, const wsmc_ssm_trace* trace);
 /* per-kernel timing of the last fused run (HIP events on the ctx stream), ms */
 typedef struct {
     double total_ms;            /* whole run, first kernel to last                       */

@@ -18,7 +18,14 @@ warm-up run, the best of 2:
   lgssm leg only lgssm1d_run (k_lgssm_segment) beside ssm_run of the LGSSM spec (k_ssm_segment)
 
 One JSON line per child, appended to profiles/ssm_fused.jsonl. Diagnostics for DESIGN.md §4;
-bench.py stays the headline."""
+bench.py stays the headline.
+
+    python tools/bench_ssm.py --trace                    every model at T = 1e4, 1e5
+    python tools/bench_ssm.py --trace --leg sv --T 10000
+
+The trace leg (wsmc_ssm_run_traced): the persistent run untraced, traced, and the only other way to
+the same rows, spec.statements(ctx, data, trace=True), which waits at every step. Same protocol
+(the statements' warm-up is at most 1000 steps long); lines go to profiles/ssm_trace.jsonl."""
 import argparse
 import json
 import pathlib
@@ -32,6 +39,7 @@ sys.path[:0] = [str(ROOT / "weightedsampling.jl_amd"), str(ROOT / "oracle"), str
 N = 1000
 LEGS = ["sv", "poisson_count", "kitagawa", "local_trend", "lgssm"]
 OUT = ROOT / "profiles" / "ssm_fused.jsonl"
+OUT_TRACE = ROOT / "profiles" / "ssm_trace.jsonl"
 
 
 def best_of(run, reps=2):
@@ -121,13 +129,62 @@ def child(leg: str, T: int) -> dict:
     return out
 
 
-def driver(Ts, legs) -> int:
+def child_trace(leg: str, T: int) -> dict:
+    import numpy as np
+    import wsmc
+    from wsmc import models
+    if leg == "lgssm":
+        spec, data = models.lgssm1d_spec(), models.lgssm1d_data(T)
+    else:
+        make, gen = models.SSM_MODELS[leg]
+        spec, data = make(), gen(T)
+
+    def persistent(trace):
+        def run():
+            ctx = wsmc.Context(N, seed=42)
+            ctx.sync()
+            t0 = time.perf_counter()
+            r = ctx.ssm_run(spec, data, ess_perc_min=1.0, trace=trace)
+            dt = time.perf_counter() - t0
+            assert ctx.ssm_stats()["persistent_runs"] == 1
+            ctx.close()
+            return dt, r
+        return run
+
+    first = [True]
+
+    def statements():
+        steps = min(T, 1000) if first[0] else T   # the warm-up
+        first[0] = False
+        ctx = wsmc.Context(N, seed=42)
+        ctx.sync()
+        t0 = time.perf_counter()
+        _, _, tr = spec.statements(ctx, data[:steps], ess_perc_min=1.0, trace=True)
+        dt = time.perf_counter() - t0
+        ctx.close()
+        return dt, tr
+
+    u, ev = best_of(persistent(False))
+    p, (ev_t, tr) = best_of(persistent(True))
+    s, want = best_of(statements)
+    same = lambda a, b: bool(((a.view(np.uint64) == b.view(np.uint64)) | (np.isnan(a) & np.isnan(b))).all())
+    assert ev == ev_t and same(tr.ess, want.ess) and same(tr.log_evidence, want.log_evidence)
+    assert all(same(tr.mean[c], want.mean[c]) and same(tr.var[c], want.var[c]) for c in spec.cols)
+    return {"leg": leg, "N": N, "T": T, "columns": len(spec.cols), "step_statements": spec.spec.n_step,
+            "untraced_s": u, "untraced_us_per_step": 1e6 * u / T, "traced_s": p, "traced_us_per_step": 1e6 * p / T,
+            "trace_us_per_step": 1e6 * (p - u) / T, "statements_traced_s": s, "statements_traced_us_per_step": 1e6 * s / T,
+            "factor_vs_statements_traced": s / p, "log_evidence": ev}
+
+
+def driver(Ts, legs, trace=False) -> int:
+    out = OUT_TRACE if trace else OUT
     OUT.parent.mkdir(exist_ok=True)
     for leg in legs:
         per_step = None   # seconds a step of one child (all its routes and repetitions), from the run before
         for T in Ts:
             limit = 180 if per_step is None else int(60 + 3 * per_step * T)
             cmd = ["timeout", "-k", "10", str(limit), sys.executable, __file__, "--leg", leg, "--T", str(T)]
+            cmd += ["--trace"] if trace else []
             t0 = time.perf_counter()
             r = subprocess.run(cmd, capture_output=True, text=True)
             dt = time.perf_counter() - t0
@@ -136,7 +193,7 @@ def driver(Ts, legs) -> int:
                 return 1   # nothing more is started on the device
             line = r.stdout.strip().splitlines()[-1]
             json.loads(line)
-            with open(OUT, "a") as f:
+            with open(out, "a") as f:
                 f.write(line + "\n")
             print(line, flush=True)
             per_step = dt / T
@@ -148,8 +205,11 @@ if __name__ == "__main__":
     ap.add_argument("--leg", choices=LEGS)
     ap.add_argument("--T", type=int, action="append")
     ap.add_argument("--legs", default=",".join(LEGS))
+    ap.add_argument("--trace", action="store_true", help="the trace leg (profiles/ssm_trace.jsonl)")
     a = ap.parse_args()
     if a.leg:
-        print(json.dumps(child(a.leg, (a.T or [1000])[0])), flush=True)
+        print(json.dumps((child_trace if a.trace else child)(a.leg, (a.T or [1000])[0])), flush=True)
         sys.exit(0)
+    if a.trace:
+        sys.exit(driver(a.T or [10_000, 100_000], a.legs.split(","), trace=True))
     sys.exit(driver(a.T or [1000, 10_000, 100_000], a.legs.split(",")))

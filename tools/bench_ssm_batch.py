@@ -15,6 +15,11 @@ fails, or runs into its limit, ends the driver: nothing more is started on the d
   batch     Context.ssm_run_batch of B filters, B in {1, 16, 64, CUs, 4 CUs, 1024}; a warm-up call,
             then the best of 3. Filter 0's evidence is checked against the baseline's first run.
 
+  --trace   (with --leg batch) the same call untraced and with the per-step trace
+            (wsmc_ssm_run_batch_traced) in one process: seconds of both, the trace's share of the
+            traced call, and the device memory the trace takes, B T (2 S + 2) 8 bytes. Lines go to
+            profiles/ssm_trace.jsonl.
+
 `ratio` is batch seconds over the baseline scaled to B; the bar is ratio < 1/16 at B = CU count
 (16 is the number of processes that may hold the device at once: the only other way to fill it).
 One JSON line per child, appended to profiles/ssm_batch.jsonl (--out). Diagnostics for DESIGN.md
@@ -62,6 +67,31 @@ def baseline(T: int) -> dict:
             best = min(best, dt)
     return {"leg": "baseline", "n": N, "T": T, "runs": NBASE, "seconds": best, "seconds_per_filter": best / NBASE,
             "filter_steps_per_s": NBASE * T / best, "log_evidence_0": ev0}
+
+
+def batch_traced(T: int, B: int) -> dict:
+    import wsmc
+    from wsmc import models
+    data = models.sv_data(T)
+    specs, seeds = filters(B)
+    ctx = wsmc.Context(1, seed=1)
+    best = {False: float("inf"), True: float("inf")}
+    res = {}
+    for rep in range(3):   # the first round warms up; then the best of 2, the two calls alternating
+        for trace in (False, True):
+            t0 = time.perf_counter()
+            res[trace] = ctx.ssm_run_batch(specs, data, N, seeds, ess_perc_min=1.0, trace=trace)
+            dt = time.perf_counter() - t0
+            if rep > 0:
+                best[trace] = min(best[trace], dt)
+    st = ctx.ssm_batch_stats()
+    assert (res[True].log_evidence == res[False].log_evidence).all()
+    assert (res[True].log_evidence_trace[:, -1] == res[True].log_evidence).all()   # sv's last statement is the OBSERVE
+    ctx.close()
+    S = len(specs[0].cols)
+    return {"leg": "batch_traced", "n": N, "T": T, "B": B, "untraced_s": best[False], "traced_s": best[True],
+            "trace_share": (best[True] - best[False]) / best[True], "trace_device_bytes": B * T * (2 * S + 2) * 8,
+            "blocks_per_cu": st["blocks_per_cu"], "cus": st["cus"], "segments": st["segments"]}
 
 
 def batch(T: int, B: int, per_filter_s: float, ev0) -> dict:
@@ -144,11 +174,14 @@ if __name__ == "__main__":
     ap.add_argument("--per-filter", type=float, default=0.0)
     ap.add_argument("--ev0", type=float, default=None)
     ap.add_argument("--out", type=pathlib.Path, default=OUT)
+    ap.add_argument("--trace", action="store_true", help="with --leg batch: untraced against traced")
     a = ap.parse_args()
     if a.leg == "probe":
         print(json.dumps(probe()), flush=True)
     elif a.leg == "baseline":
         print(json.dumps(baseline(a.T)), flush=True)
+    elif a.leg == "batch" and a.trace:
+        print(json.dumps(batch_traced(a.T, a.B)), flush=True)
     elif a.leg == "batch":
         print(json.dumps(batch(a.T, a.B, a.per_filter, a.ev0)), flush=True)
     else:

@@ -780,7 +780,7 @@ int wsmc_destroy(wsmc_ctx* c) {
                     c->d_colptr, c->run_params, c->d_tape, c->run_max, c->run_rec, c->run_dec, c->anc_log, c->obs_buf, c->run_grp, c->run_rg, c->run_nfix, c->run_wcnt, c->run_w0,
                     c->vscratch, c->xscratch, c->xp, c->comb, c->anc_out, c->xbuf, c->d_comp, c->d_ctape, c->d_prog, c->rs_grp[0], c->rs_grp[1], c->rs_qs,
                     c->xpairs, c->xnb, c->xwin, c->xstat, c->w_save, c->xms, c->xanc, c->xlines, c->xpeer,
-                    c->lg_data, c->lg_trace, c->lg_rec};
+                    c->lg_data, c->lg_trace, c->lg_rec, c->ssm_rows};
     for (void* p : bufs)
         if (p) (void)hipFree(p);
     for (double* p : c->xrun)
@@ -5401,8 +5401,13 @@ static int ssm_last_observe(const wsmc_ssm_spec* sp) {
 
 // one statement through the operators, with its auto-inserted Resample. ess_out: wait on that
 // Resample for its ESS% (the trace), else it stays asynchronous
+// mom: the trace point's rows (wsmc_ssm_trace), taken between the Observe and its Resample
+struct SsmRowOut {
+    int S;
+    double *mean, *var, *logev;   // this step's row of each, null: not wanted
+};
 static int ssm_issue(wsmc_ctx* c, const wsmc_ssm_stmt& s, const int32_t* ids, const double* row, double ess_min,
-                     int32_t scheme, double* ess_out) {
+                     int32_t scheme, double* ess_out, const SsmRowOut* mom = nullptr) {
     int rc;
     switch (s.kind) {
         case WSMC_SSM_SAMPLE: {
@@ -5437,23 +5442,46 @@ static int ssm_issue(wsmc_ctx* c, const wsmc_ssm_stmt& s, const int32_t* ids, co
             wsmc_operand x[4];
             for (int k = 0; k < 4; ++k) x[k] = ssm_map_operand(s.value, ids, row);
             if ((rc = wsmc_observe(c, &d, x))) return rc;
+            if (mom && (mom->mean || mom->var)) {
+                wsmc_operand e[4];
+                for (int k = 0; k < 4; ++k) {
+                    std::memset(&e[k], 0, sizeof(e[k]));
+                    e[k].col[0] = ids[k < mom->S ? k : 0];
+                    e[k].col[1] = -1;
+                    e[k].coef[0] = 1.0;
+                }
+                double m[4], cv[16];
+                if ((rc = wsmc_weighted_moments(c, e, mom->S, m, mom->var ? cv : nullptr))) return rc;
+                for (int k = 0; k < mom->S; ++k) {
+                    if (mom->mean) mom->mean[k] = m[k];
+                    if (mom->var) mom->var[k] = cv[k * mom->S + k];
+                }
+            }
+            if (mom && mom->logev && (rc = wsmc_log_evidence(c, mom->logev))) return rc;
             int32_t rs = 0;
-            return wsmc_resample(c, ess_min, scheme, ess_out ? &rs : nullptr, ess_out);
+            const bool waits = ess_out || mom;   // the trace's Resample waits, with or without an ESS buffer
+            return wsmc_resample(c, ess_min, scheme, waits ? &rs : nullptr, ess_out);
         }
     }
 }
 // the statement route: the spec's statements as a loop over the operators (any handle, any N, any
 // scheme); it is the definition of the run's results
 static int ssm_statements(wsmc_ctx* c, const wsmc_ssm_spec* sp, const int32_t* ids, const double* data, int32_t T,
-                          double ess_min, int32_t scheme, double* ess_trace) {
+                          double ess_min, int32_t scheme, const wsmc_ssm_trace& tr) {
+    double* ess_trace = tr.ess;
+    const bool moms = tr.mean || tr.var || tr.log_evidence;
+    const size_t S = (size_t)sp->n_cols;
     int rc;
     for (int q = 0; q < sp->n_init; ++q)
         if ((rc = ssm_issue(c, sp->init[q], ids, nullptr, ess_min, scheme, nullptr))) return rc;
     const int last = ssm_last_observe(sp);
     for (int32_t t = 0; t < T; ++t) {
         const double* row = data ? data + (size_t)t * sp->data_dim : nullptr;
+        const SsmRowOut mom = {sp->n_cols, tr.mean ? tr.mean + t * S : nullptr, tr.var ? tr.var + t * S : nullptr,
+                               tr.log_evidence ? tr.log_evidence + t : nullptr};
         for (int q = 0; q < sp->n_step; ++q)
-            if ((rc = ssm_issue(c, sp->step[q], ids, row, ess_min, scheme, ess_trace && q == last ? ess_trace + t : nullptr)))
+            if ((rc = ssm_issue(c, sp->step[q], ids, row, ess_min, scheme, ess_trace && q == last ? ess_trace + t : nullptr,
+                                moms && q == last ? &mom : nullptr)))
                 return rc;
     }
     return wsmc_sync(c);
@@ -5488,8 +5516,16 @@ static SsmStmt ssm_dev_stmt(const wsmc_ssm_stmt& s, SsmIns* ins, int* nins) {
     return r;
 }
 
-int wsmc_ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int32_t T, double ess_min, int32_t scheme,
-                 double* log_evidence_out, double* ess_trace_out) {
+int wsmc_ssm_trace_sizeof(int64_t* bytes) {
+    if (!bytes) return fail(WSMC_EARG, "null argument");
+    *bytes = (int64_t)sizeof(wsmc_ssm_trace);
+    return WSMC_OK;
+}
+
+// wsmc_ssm_run and wsmc_ssm_run_traced: tr's members are null where nothing is wanted
+static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int32_t T, double ess_min, int32_t scheme,
+                   double* log_evidence_out, const wsmc_ssm_trace& tr) {
+    double* const ess_trace_out = tr.ess;
     if (!c) return fail(WSMC_EARG, "null context");
     if (int rc = wsmc_ssm_spec_check(sp)) return rc;
     if (T < 1 || (sp->data_dim > 0 && !data)) return fail(WSMC_EARG, "bad arguments");
@@ -5530,7 +5566,7 @@ int wsmc_ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int32
     for (int k = 0; k < S; ++k)   // the missing ones, in order
         if (int rc = wsmc_col_create(c, sp->col_names[k], 1, &ids[k])) return rc;
     if (!persistent) {
-        int rc = ssm_statements(c, sp, ids, data, T, ess_min, scheme, ess_trace_out);
+        int rc = ssm_statements(c, sp, ids, data, T, ess_min, scheme, tr);
         if (rc) return rc;
         sc->ssm_stmt_runs += 1;
         sc->ssm_book_us = 0;
@@ -5563,11 +5599,24 @@ int wsmc_ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int32
         c->lg_trace_cap = T;
     }
     if (!c->lg_rec) WSMC_HIP(hipMalloc(&c->lg_rec, sizeof(LgRecord)));
+    // the trace's rows: a buffer of the context, as the ESS trace's is, grown to what was asked
+    const size_t n_mean = tr.mean ? (size_t)T * S : 0, n_var = tr.var ? (size_t)T * S : 0, n_le = tr.log_evidence ? (size_t)T : 0;
+    if ((int64_t)(n_mean + n_var + n_le) > c->ssm_rows_cap) {
+        WSMC_HIP(ctx_sync(c, c->stream));
+        if (c->ssm_rows) WSMC_HIP(hipFree(c->ssm_rows));
+        c->ssm_rows = nullptr;
+        c->ssm_rows_cap = 0;
+        WSMC_HIP(hipMalloc(&c->ssm_rows, sizeof(double) * (n_mean + n_var + n_le)));
+        c->ssm_rows_cap = (int64_t)(n_mean + n_var + n_le);
+    }
     if (ndata > 0)
         WSMC_HIP(hipMemcpyAsync(c->lg_data, data, sizeof(double) * (size_t)ndata, hipMemcpyHostToDevice, c->stream));
     WSMC_HIP(hipMemsetAsync(c->lg_rec, 0, sizeof(LgRecord), c->stream));
     SsmArgs ka;
     std::memset(&ka, 0, sizeof(ka));
+    ka.tr_mean = n_mean ? c->ssm_rows : nullptr;
+    ka.tr_var = n_var ? c->ssm_rows + n_mean : nullptr;
+    ka.tr_logev = n_le ? c->ssm_rows + n_mean + n_var : nullptr;
     for (int k = 0; k < S; ++k) ka.x[k] = c->cols[ids[k]].front;
     ka.w = c->w;
     ka.anc = c->anc;
@@ -5606,6 +5655,9 @@ int wsmc_ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int32
     if (ess_trace_out)
         WSMC_HIP(hipMemcpyAsync(ess_trace_out, c->lg_trace, sizeof(double) * (size_t)T, hipMemcpyDeviceToHost,
                                 c->stream));
+    if (n_mean) WSMC_HIP(hipMemcpyAsync(tr.mean, ka.tr_mean, sizeof(double) * n_mean, hipMemcpyDeviceToHost, c->stream));
+    if (n_var) WSMC_HIP(hipMemcpyAsync(tr.var, ka.tr_var, sizeof(double) * n_var, hipMemcpyDeviceToHost, c->stream));
+    if (n_le) WSMC_HIP(hipMemcpyAsync(tr.log_evidence, ka.tr_logev, sizeof(double) * n_le, hipMemcpyDeviceToHost, c->stream));
     // the bookkeeping of the statements issued one by one, while the device runs
     const auto t_book = clk::now();
     for (int k = 0; k < S; ++k) wrote_col(c, ids[k]);
@@ -5649,6 +5701,18 @@ int wsmc_ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int32
         if (int rc = wsmc_log_evidence(c, log_evidence_out)) return rc;
     c->ssm_wall_us = us(t_in, clk::now());
     return WSMC_OK;
+}
+
+int wsmc_ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int32_t T, double ess_min, int32_t scheme,
+                 double* log_evidence_out, double* ess_trace_out) {
+    const wsmc_ssm_trace tr = {ess_trace_out, nullptr, nullptr, nullptr};
+    return ssm_run(c, sp, data, T, ess_min, scheme, log_evidence_out, tr);
+}
+
+int wsmc_ssm_run_traced(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int32_t T, double ess_min, int32_t scheme,
+                        double* log_evidence_out, const wsmc_ssm_trace* trace) {
+    const wsmc_ssm_trace none = {nullptr, nullptr, nullptr, nullptr};
+    return ssm_run(c, sp, data, T, ess_min, scheme, log_evidence_out, trace ? *trace : none);
 }
 
 int wsmc_debug_ssm(wsmc_ctx* c, int32_t segment_steps, int64_t* stats_out) {
@@ -5737,9 +5801,10 @@ int wsmc_ssm_batch_out_sizeof(int64_t* bytes) {
     return WSMC_OK;
 }
 
-int wsmc_ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_specs, const double* data, int32_t n_tables,
-                       int32_t T, int32_t n, int32_t B, const uint64_t* seeds, double ess_min, int32_t scheme,
-                       wsmc_ssm_batch_out* out) {
+// wsmc_ssm_run_batch and wsmc_ssm_run_batch_traced: tr's members are null where nothing is wanted
+static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_specs, const double* data, int32_t n_tables,
+                         int32_t T, int32_t n, int32_t B, const uint64_t* seeds, double ess_min, int32_t scheme,
+                         wsmc_ssm_batch_out* out, const wsmc_ssm_trace& tr) {
     // every refusal before any device call; the context's state is never read past its layout
     if (!c) return fail(WSMC_EARG, "null context");
     if (c->multi || is_sharded(c)) return fail(WSMC_EARG, "ssm batch: a sharded or multi-device context (one unsharded device runs a batch)");
@@ -5801,13 +5866,15 @@ int wsmc_ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_specs,
     const size_t nx = up(sizeof(double) * (size_t)B * S * n), nw = up(sizeof(double) * (size_t)B * n),
                  nanc = up(sizeof(int32_t) * (size_t)B * n), nrec = up(sizeof(SsmBatchRec) * (size_t)B),
                  nfilt = up(sizeof(SsmBatchFilter) * (size_t)B), ndata = up(sizeof(double) * (size_t)n_tables * T * dd),
-                 ntrace = out->ess_trace ? up(sizeof(double) * (size_t)B * T) : 0;
+                 ntrace = out->ess_trace || tr.ess ? up(sizeof(double) * (size_t)B * T) : 0,
+                 nmean = tr.mean ? up(sizeof(double) * (size_t)B * T * S) : 0, nvar = tr.var ? up(sizeof(double) * (size_t)B * T * S) : 0,
+                 nle = tr.log_evidence ? up(sizeof(double) * (size_t)B * T) : 0;
     const size_t nstate = nx + nw + nanc + nrec;
     struct Slab {
         char* p = nullptr;
         ~Slab() { if (p) (void)hipFree(p); }
     } slab;
-    WSMC_HIP(hipMalloc(&slab.p, nstate + nfilt + ndata + ntrace + 256));
+    WSMC_HIP(hipMalloc(&slab.p, nstate + nfilt + ndata + ntrace + nmean + nvar + nle + 256));
     char* q = slab.p;
     double* d_x = reinterpret_cast<double*>(q); q += nx;
     double* d_w = reinterpret_cast<double*>(q); q += nw;
@@ -5815,7 +5882,10 @@ int wsmc_ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_specs,
     SsmBatchRec* d_rec = reinterpret_cast<SsmBatchRec*>(q); q += nrec;
     SsmBatchFilter* d_filt = reinterpret_cast<SsmBatchFilter*>(q); q += nfilt;
     double* d_data = reinterpret_cast<double*>(q); q += ndata;
-    double* d_trace = ntrace ? reinterpret_cast<double*>(q) : nullptr;
+    double* d_trace = ntrace ? reinterpret_cast<double*>(q) : nullptr; q += ntrace;
+    double* d_mean = nmean ? reinterpret_cast<double*>(q) : nullptr; q += nmean;
+    double* d_var = nvar ? reinterpret_cast<double*>(q) : nullptr; q += nvar;
+    double* d_le = nle ? reinterpret_cast<double*>(q) : nullptr;
     for (int32_t b = 0; b < B; ++b)
         filt[(size_t)b].data = dd > 0 ? d_data + (size_t)(n_tables == 1 ? 0 : b) * T * dd : nullptr;
     hipStream_t st = c->stream;
@@ -5834,6 +5904,9 @@ int wsmc_ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_specs,
     ka.w = d_w;
     ka.anc = d_anc;
     ka.ess_trace = d_trace;
+    ka.tr_mean = d_mean;
+    ka.tr_var = d_var;
+    ka.tr_logev = d_le;
     ka.rec = d_rec;
     ka.filt = d_filt;
     ka.N = n;
@@ -5853,7 +5926,7 @@ int wsmc_ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_specs,
     // steps a launch: the single run's, divided by the rounds of resident workgroups the batch
     // takes, so a launch stays near the single run's 25 ms whatever B is
     int per_cu = 0, cus = 0;
-    if (e == hipSuccess) e = ssm_batch_occupancy(c->device, feat, threads, ssm_lds_bytes(n, S), &per_cu, &cus);
+    if (e == hipSuccess) e = ssm_batch_occupancy(c->device, feat, d_mean || d_var || d_le, threads, ssm_lds_bytes(n, S), &per_cu, &cus);
     if (e == hipSuccess && (per_cu < 1 || cus < 1)) e = hipErrorInvalidValue;
     int64_t nseg = 0;
     if (e == hipSuccess) {
@@ -5875,6 +5948,10 @@ int wsmc_ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_specs,
     };
     down(hrec.data(), d_rec, sizeof(SsmBatchRec) * (size_t)B);
     down(out->ess_trace, d_trace, sizeof(double) * (size_t)B * T);
+    down(tr.ess, d_trace, sizeof(double) * (size_t)B * T);
+    down(tr.mean, d_mean, sizeof(double) * (size_t)B * T * S);
+    down(tr.var, d_var, sizeof(double) * (size_t)B * T * S);
+    down(tr.log_evidence, d_le, sizeof(double) * (size_t)B * T);
     down(out->cols, d_x, sizeof(double) * (size_t)B * S * n);
     down(out->log_weights, d_w, sizeof(double) * (size_t)B * n);
     down(out->last_ancestors, d_anc, sizeof(int32_t) * (size_t)B * n);
@@ -5901,6 +5978,20 @@ int wsmc_ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_specs,
     c->ssm_batch_segments = nseg;
     c->ssm_batch_wall_us = (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(clk::now() - t_in).count();
     return WSMC_OK;
+}
+
+int wsmc_ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_specs, const double* data, int32_t n_tables,
+                       int32_t T, int32_t n, int32_t B, const uint64_t* seeds, double ess_min, int32_t scheme,
+                       wsmc_ssm_batch_out* out) {
+    const wsmc_ssm_trace none = {nullptr, nullptr, nullptr, nullptr};
+    return ssm_run_batch(c, specs, n_specs, data, n_tables, T, n, B, seeds, ess_min, scheme, out, none);
+}
+
+int wsmc_ssm_run_batch_traced(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_specs, const double* data, int32_t n_tables,
+                              int32_t T, int32_t n, int32_t B, const uint64_t* seeds, double ess_min, int32_t scheme,
+                              wsmc_ssm_batch_out* out, const wsmc_ssm_trace* trace) {
+    const wsmc_ssm_trace none = {nullptr, nullptr, nullptr, nullptr};
+    return ssm_run_batch(c, specs, n_specs, data, n_tables, T, n, B, seeds, ess_min, scheme, out, trace ? *trace : none);
 }
 
 int wsmc_debug_ssm_batch(wsmc_ctx* c, int32_t segment_steps, int64_t* stats_out) {

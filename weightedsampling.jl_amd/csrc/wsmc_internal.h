@@ -383,6 +383,8 @@ struct wsmc_ctx {
     int32_t ssm_segment = 0;                // steps per launch (0: kSsmSegmentStmts / the step's statements)
     int64_t ssm_runs = 0, ssm_stmt_runs = 0, ssm_segments = 0;   // cumulative (wsmc_debug_ssm)
     int64_t ssm_book_us = 0, ssm_wall_us = 0;
+    double* ssm_rows = nullptr;             // [ssm_rows_cap] a traced run's rows: means, variances, evidence (wsmc_ssm_run_traced)
+    int64_t ssm_rows_cap = 0;
     // wsmc_ssm_run_batch (it touches nothing else of the context): steps per launch (0: the
     // default), then the last call's resident blocks per CU, CU count, segments and wall time
     int32_t ssm_batch_segment = 0;
@@ -948,6 +950,9 @@ struct SsmArgs {
     int32_t* anc;             // [N] written when a step of the segment resampled
     const double* data;       // [T x data_dim] row-major
     double* ess_trace;        // [T] or null
+    double* tr_mean;          // a traced run's rows (wsmc_ssm_run_traced), each null when not wanted:
+    double* tr_var;           //   [T][S] the columns' weighted means and variances,
+    double* tr_logev;         //   [T] the log evidence, at the ESS trace's point
     LgRecord* rec;
     int32_t N, P;             // particles, particles per thread
     int32_t S, data_dim;      // columns
@@ -966,6 +971,7 @@ static_assert(sizeof(SsmArgs) + 32 <= 4096, "the spec rides in the kernel argume
 size_t ssm_lds_bytes(int n, int S);
 // feat: WSMC_FEAT_EXT / WSMC_FEAT_GAM bits over the spec's dists (the kernel's instantiation)
 int ssm_threads(unsigned feat, int n);
+// (the traced instantiation when a tr_ pointer is set, else the one an untraced run has always had)
 hipError_t launch_ssm_segment(hipStream_t s, const SsmArgs& a, unsigned feat, int threads);
 // B independent runs of that kernel's step body in one launch, one workgroup a filter
 // (csrc/wsmc_ssm_batch.hip, wsmc_ssm_run_batch). The statements' shape is one for the batch, their
@@ -990,6 +996,9 @@ struct SsmBatchArgs {
     double* w;                // [B][N] log-weights
     int32_t* anc;             // [B][N] row b written when a step of the segment resampled
     double* ess_trace;        // [B][T] or null
+    double* tr_mean;          // a traced batch's rows, each null when not wanted: [B][T][S],
+    double* tr_var;           //   [B][T][S],
+    double* tr_logev;         //   [B][T]
     SsmBatchRec* rec;         // [B]
     const SsmBatchFilter* filt;   // [B]
     int32_t N, P;             // particles, particles per thread
@@ -1003,7 +1012,7 @@ struct SsmBatchArgs {
     double ess_min;
 };
 // blocks of the variant that are resident on one CU (by registers, waves and LDS), and the device's CUs
-hipError_t ssm_batch_occupancy(int device, unsigned feat, int threads, size_t lds, int* per_cu, int* cus);
+hipError_t ssm_batch_occupancy(int device, unsigned feat, bool traced, int threads, size_t lds, int* per_cu, int* cus);
 hipError_t launch_ssm_batch_segment(hipStream_t s, const SsmBatchArgs& a, unsigned feat, int threads);
 // one handle over several devices (wsmc_multi.hip): the ABI entry points fan out
 int multi_destroy(wsmc_ctx* c);

@@ -26,12 +26,27 @@
 
 namespace wsmc {
 
+// This file is compiled twice: as it stands for the untraced instantiations, and through
+// csrc/wsmc_ssm_traced.hip, which defines WSMC_SSM_TRACED, for the traced ones. A translation
+// unit of their own keeps the untraced kernels what the compiler made of them before there was a
+// trace: with six kernels in one unit instead of three the inliner's choices change and the
+// log-Gamma variant goes from 116 VGPRs to 128 and spills.
+#ifdef WSMC_SSM_TRACED
+constexpr bool kSsTraced = true;
+#define WSMC_SSM_VARIANTS ssm_launch_traced
+#else
+constexpr bool kSsTraced = false;
+#define WSMC_SSM_VARIANTS ssm_launch_untraced
+
 // the kernel's dynamic LDS for n particles in S columns (beside the 4 KiB of static log / exp tables)
 size_t ssm_lds_bytes(int n, int S) {
     return ((size_t)S + 2) * ss_n8(n) * sizeof(double) + ss_n4(n) * sizeof(int32_t) + kSsScratch * sizeof(uint64_t);
 }
+#endif
 
-template <unsigned FEAT, int THREADS>
+// TR: the traced run (wsmc_ssm_run_traced), which also leaves row t of the moments and the evidence
+// at the ESS trace's point
+template <unsigned FEAT, int THREADS, bool TR>
 __global__ __launch_bounds__(THREADS) void k_ssm_segment(SsmArgs) {
     const SsmArgs& a = *(const SsmArgs*)(const char*)__builtin_amdgcn_kernarg_segment_ptr();
     extern __shared__ __attribute__((aligned(16))) char ss_smem[];
@@ -93,7 +108,11 @@ __global__ __launch_bounds__(THREADS) void k_ssm_segment(SsmArgs) {
             if (st.kind == WSMC_SSM_SAMPLE) {
                 op += 2;   // the draws, then a Resample that does not run (the weights have not changed)
             } else if (st.kind == WSMC_SSM_OBSERVE) {
-                const SsDecision d = ss_resample(L, K, a.ess_min, a.scheme, a.seed, op);
+                const bool row = TR && !init && q == a.last_obs;
+                if (row && (a.tr_mean || a.tr_var))
+                    ss_trace_row(L, a.tr_mean ? a.tr_mean + (size_t)t * S : nullptr, a.tr_var ? a.tr_var + (size_t)t * S : nullptr);
+                const SsDecision d = ss_resample<TR>(L, K, a.ess_min, a.scheme, a.seed, op);
+                if (row && a.tr_logev && tid == 0) a.tr_logev[t] = d.logev;
                 op += 1;
                 nres += d.resampled;
                 last_dec = d.resampled;
@@ -119,22 +138,31 @@ __global__ __launch_bounds__(THREADS) void k_ssm_segment(SsmArgs) {
     }
 }
 
+template <unsigned FEAT, int THREADS>
+static hipError_t ssm_launch(hipStream_t s, const SsmArgs& a, int threads, size_t lds) {
+    if (lds > 65536 - 4096) {   // past 64 KiB a kernel must ask for its dynamic LDS (per device: set at each launch)
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ssm_segment<FEAT, THREADS, kSsTraced>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((k_ssm_segment<FEAT, THREADS, kSsTraced>), dim3(1), dim3(threads), lds, s, a);
+    return hipGetLastError();
+}
+// this unit's three feature variants (launch_ssm_segment has checked the arguments)
+hipError_t WSMC_SSM_VARIANTS(hipStream_t s, const SsmArgs& a, unsigned feat, int threads, size_t lds) {
+    if (feat & WSMC_FEAT_GAM) return ssm_launch<kSsFeatGam, kSsGamThreads>(s, a, threads, lds);
+    if (feat & WSMC_FEAT_EXT) return ssm_launch<kSsFeatExt, kSsMaxThreads>(s, a, threads, lds);
+    return ssm_launch<0u, kSsMaxThreads>(s, a, threads, lds);
+}
+
+#ifndef WSMC_SSM_TRACED
 int ssm_threads(unsigned feat, int n) {
     const int cap = (feat & WSMC_FEAT_GAM) ? kSsGamThreads : kSsMaxThreads;
     // two particles a thread where the workgroup allows (wsmc_lgssm1d_run's measured choice)
     return std::max(64, std::min(cap, ((n + 127) / 128) * 64));
 }
 
-template <unsigned FEAT, int THREADS>
-static hipError_t ssm_launch(hipStream_t s, const SsmArgs& a, int threads, size_t lds) {
-    if (lds > 65536 - 4096) {   // past 64 KiB a kernel must ask for its dynamic LDS (per device: set at each launch)
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ssm_segment<FEAT, THREADS>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((k_ssm_segment<FEAT, THREADS>), dim3(1), dim3(threads), lds, s, a);
-    return hipGetLastError();
-}
+hipError_t ssm_launch_traced(hipStream_t s, const SsmArgs& a, unsigned feat, int threads, size_t lds);   // csrc/wsmc_ssm_traced.hip
 
 hipError_t launch_ssm_segment(hipStream_t s, const SsmArgs& a, unsigned feat, int threads) {
     const int tmax = (feat & WSMC_FEAT_GAM) ? kSsGamThreads : kSsMaxThreads;
@@ -145,9 +173,9 @@ hipError_t launch_ssm_segment(hipStream_t s, const SsmArgs& a, unsigned feat, in
         return hipErrorInvalidValue;
     const size_t lds = ssm_lds_bytes(a.N, a.S);
     if (lds + 4096 > 160 * 1024) return hipErrorInvalidValue;   // with the static tables: the workgroup's LDS
-    if (feat & WSMC_FEAT_GAM) return ssm_launch<kSsFeatGam, kSsGamThreads>(s, a, threads, lds);
-    if (feat & WSMC_FEAT_EXT) return ssm_launch<kSsFeatExt, kSsMaxThreads>(s, a, threads, lds);
-    return ssm_launch<0u, kSsMaxThreads>(s, a, threads, lds);
+    if (a.tr_mean || a.tr_var || a.tr_logev) return ssm_launch_traced(s, a, feat, threads, lds);
+    return ssm_launch_untraced(s, a, feat, threads, lds);
 }
+#endif
 
 }  // namespace wsmc

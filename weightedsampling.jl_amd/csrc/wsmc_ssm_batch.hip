@@ -21,11 +21,24 @@
 
 namespace wsmc {
 
+// compiled twice, as csrc/wsmc_ssm.hip is: as it stands for the untraced instantiations, through
+// csrc/wsmc_ssm_batch_traced.hip (WSMC_SSM_TRACED) for the traced ones
+#ifdef WSMC_SSM_TRACED
+constexpr bool kSsbTraced = true;
+#define WSMC_SSB_OCCUPANCY ssb_occupancy_traced
+#define WSMC_SSB_VARIANTS ssb_launch_traced
+#else
+constexpr bool kSsbTraced = false;
+#define WSMC_SSB_OCCUPANCY ssb_occupancy_untraced
+#define WSMC_SSB_VARIANTS ssb_launch_untraced
+#endif
+
 namespace {
 typedef const SsmBatchFilter __attribute__((address_space(4))) * SsFilterPtr;
 }
 
-template <unsigned FEAT, int THREADS>
+// TR: the traced batch (wsmc_ssm_run_batch_traced), k_ssm_segment's flag
+template <unsigned FEAT, int THREADS, bool TR>
 __global__ __launch_bounds__(THREADS) void k_ssm_batch_segment(const SsmBatchArgs a) {
     extern __shared__ __attribute__((aligned(16))) char ssb_smem[];
     const int tid = (int)threadIdx.x, nthr = (int)blockDim.x;
@@ -93,7 +106,12 @@ __global__ __launch_bounds__(THREADS) void k_ssm_batch_segment(const SsmBatchArg
             if (st.kind == WSMC_SSM_SAMPLE) {
                 op += 2;   // the draws, then a Resample that does not run (the weights have not changed)
             } else if (st.kind == WSMC_SSM_OBSERVE) {
-                const SsDecision d = ss_resample(L, K, a.ess_min, a.scheme, seed, op);
+                const bool row = TR && !init && q == a.last_obs;
+                const size_t r = b * (size_t)a.T + (size_t)t;
+                if (row && (a.tr_mean || a.tr_var))
+                    ss_trace_row(L, a.tr_mean ? a.tr_mean + r * S : nullptr, a.tr_var ? a.tr_var + r * S : nullptr);
+                const SsDecision d = ss_resample<TR>(L, K, a.ess_min, a.scheme, seed, op);
+                if (row && a.tr_logev && tid == 0) a.tr_logev[r] = d.logev;
                 op += 1;
                 nres += d.resampled;
                 last_dec = d.resampled;
@@ -169,7 +187,7 @@ namespace {
 
 template <unsigned FEAT, int THREADS>
 hipError_t ssb_occupancy(int threads, size_t lds, int* per_cu) {
-    const void* k = reinterpret_cast<const void*>(k_ssm_batch_segment<FEAT, THREADS>);
+    const void* k = reinterpret_cast<const void*>(k_ssm_batch_segment<FEAT, THREADS, kSsbTraced>);
     if (lds > 65536 - 4096) {   // the occupancy query refuses dynamic LDS the kernel has not asked for
         const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
@@ -180,23 +198,36 @@ hipError_t ssb_occupancy(int threads, size_t lds, int* per_cu) {
 template <unsigned FEAT, int THREADS>
 hipError_t ssb_launch(hipStream_t s, const SsmBatchArgs& a, int threads, size_t lds) {
     if (lds > 65536 - 4096) {   // past 64 KiB a kernel must ask for its dynamic LDS (per device: set at each launch)
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ssm_batch_segment<FEAT, THREADS>),
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ssm_batch_segment<FEAT, THREADS, kSsbTraced>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((k_ssm_batch_segment<FEAT, THREADS>), dim3((unsigned)a.B), dim3(threads), lds, s, a);
+    hipLaunchKernelGGL((k_ssm_batch_segment<FEAT, THREADS, kSsbTraced>), dim3((unsigned)a.B), dim3(threads), lds, s, a);
     return hipGetLastError();
 }
 
 }  // namespace
 
-hipError_t ssm_batch_occupancy(int device, unsigned feat, int threads, size_t lds, int* per_cu, int* cus) {
-    hipError_t e = hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, device);
+// this unit's three feature variants
+hipError_t WSMC_SSB_OCCUPANCY(unsigned feat, int threads, size_t lds, int* per_cu) {
+    if (feat & WSMC_FEAT_GAM) return ssb_occupancy<kSsFeatGam, kSsGamThreads>(threads, lds, per_cu);
+    if (feat & WSMC_FEAT_EXT) return ssb_occupancy<kSsFeatExt, kSsMaxThreads>(threads, lds, per_cu);
+    return ssb_occupancy<0u, kSsMaxThreads>(threads, lds, per_cu);
+}
+hipError_t WSMC_SSB_VARIANTS(hipStream_t s, const SsmBatchArgs& a, unsigned feat, int threads, size_t lds) {
+    if (feat & WSMC_FEAT_GAM) return ssb_launch<kSsFeatGam, kSsGamThreads>(s, a, threads, lds);
+    if (feat & WSMC_FEAT_EXT) return ssb_launch<kSsFeatExt, kSsMaxThreads>(s, a, threads, lds);
+    return ssb_launch<0u, kSsMaxThreads>(s, a, threads, lds);
+}
+
+#ifndef WSMC_SSM_TRACED
+hipError_t ssb_occupancy_traced(unsigned feat, int threads, size_t lds, int* per_cu);   // csrc/wsmc_ssm_batch_traced.hip
+hipError_t ssb_launch_traced(hipStream_t s, const SsmBatchArgs& a, unsigned feat, int threads, size_t lds);
+
+hipError_t ssm_batch_occupancy(int device, unsigned feat, bool traced, int threads, size_t lds, int* per_cu, int* cus) {
+    const hipError_t e = hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, device);
     if (e != hipSuccess) return e;
-    if (feat & WSMC_FEAT_GAM) e = ssb_occupancy<kSsFeatGam, kSsGamThreads>(threads, lds, per_cu);
-    else if (feat & WSMC_FEAT_EXT) e = ssb_occupancy<kSsFeatExt, kSsMaxThreads>(threads, lds, per_cu);
-    else e = ssb_occupancy<0u, kSsMaxThreads>(threads, lds, per_cu);
-    return e;
+    return traced ? ssb_occupancy_traced(feat, threads, lds, per_cu) : ssb_occupancy_untraced(feat, threads, lds, per_cu);
 }
 
 hipError_t launch_ssm_batch_segment(hipStream_t s, const SsmBatchArgs& a, unsigned feat, int threads) {
@@ -208,9 +239,9 @@ hipError_t launch_ssm_batch_segment(hipStream_t s, const SsmBatchArgs& a, unsign
         return hipErrorInvalidValue;
     const size_t lds = ssm_lds_bytes(a.N, a.S);
     if (lds + 4096 > 160 * 1024) return hipErrorInvalidValue;   // with the static tables: the workgroup's LDS
-    if (feat & WSMC_FEAT_GAM) return ssb_launch<kSsFeatGam, kSsGamThreads>(s, a, threads, lds);
-    if (feat & WSMC_FEAT_EXT) return ssb_launch<kSsFeatExt, kSsMaxThreads>(s, a, threads, lds);
-    return ssb_launch<0u, kSsMaxThreads>(s, a, threads, lds);
+    if (a.tr_mean || a.tr_var || a.tr_logev) return ssb_launch_traced(s, a, feat, threads, lds);
+    return ssb_launch_untraced(s, a, feat, threads, lds);
 }
+#endif
 
 }  // namespace wsmc

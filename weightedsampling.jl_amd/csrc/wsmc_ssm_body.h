@@ -189,12 +189,15 @@ __device__ inline void ss_statement(const SsmStmt& st, const SsmIns* ins, SsStat
 // what a Resample that ran leaves for the block
 struct SsDecision {
     double ess;
+    double logev;        // a traced run: wsmc_log_evidence of the weights the Resample met
     int resampled;
 };
 
 // Resample on the block's log-weights (wsmc_lgssm.hip's, its arithmetic unchanged): the ESS and
 // the strict decision; a resampling step gathers every column and resets the weights to the
-// log-mean. Every thread calls it (it holds barriers). op: the Resample's op counter.
+// log-mean. Every thread calls it (it holds barriers). op: the Resample's op counter. TR: a traced
+// run, whose first wave also finishes the evidence from the sums it holds.
+template <bool TR>
 __device__ inline SsDecision ss_resample(SsState& L, int K, double ess_min, int scheme, uint64_t seed, uint64_t op) {
     const int N = L.N, i0 = L.i0, i1 = L.i1, lane = L.lane, wave = L.wave, nw = L.nw;
     uint64_t* red0 = L.red;
@@ -251,6 +254,10 @@ __device__ inline SsDecision ss_resample(SsState& L, int K, double ess_min, int 
                 bc[1] = go ? 1u : 0u;
                 bc[2] = st.Q;
             }
+            if (TR) {
+                const double le = wsmc_global_log_evidence(&st, 1);
+                if (lane == 0) bc[4] = wsmc_d2bits(le);
+            }
         }
         if (wave == nw - 1 && st.Q > 0) {   // (one wave: it does both in turn)
             const double mean = wsmc_shard_mean(&st);
@@ -260,6 +267,7 @@ __device__ inline SsDecision ss_resample(SsState& L, int K, double ess_min, int 
     __syncthreads();
     SsDecision dec;
     dec.ess = wsmc_bits2d(bc[0]);
+    dec.logev = TR ? wsmc_bits2d(bc[4]) : 0.0;
     dec.resampled = bc[1] != 0 ? 1 : 0;
     if (!dec.resampled) return dec;   // uniform over the block
     const uint64_t Q = bc[2];
@@ -335,6 +343,120 @@ __device__ inline SsDecision ss_resample(SsState& L, int K, double ess_min, int 
     // CDF behind the next Resample's first barrier
     L.off = L.off == 0 ? L.S : L.off - 1;
     return dec;
+}
+
+// ---- the traced run's row (wsmc_ssm_run_traced): wsmc_weighted_moments of the columns -----------
+// The sums are the canonical ones (oracle/wsmc_oracle.c canon_block, csrc/wsmc_kernels.hip
+// k_moments / k_moments_final): tiles of 2048 items, canonical thread th of 256 adding items
+// base + j * 256 + th, j = 0..7, from 0.0 (0.0 past N); an xor butterfly 1, 2, .., 32 over each 64
+// lanes; (w0 + w1) + (w2 + w3); the tile partials through the same block shape. A thread here
+// owns consecutive particles and the block has 64..1024 threads, so the unit of work is a
+// canonical wave (64 lanes x 8 strided items, 4 to a tile) of one of the values, dealt over the
+// block's waves.
+constexpr int kSsCanonWaves = 4 * ((kLgCap + 2047) / 2048);   // 12: three tiles at the largest cap
+constexpr int kSsTrVals = 1 + WSMC_SSM_MAX_COLS;              // pass 1: e and e z_k
+static_assert(kSsCanonWaves * (kSsTrVals + WSMC_SSM_MAX_COLS) <= 2 * kSsWaves * 4,
+              "both passes' wave totals fit the reduction scratch");
+
+// a thread's canonical items of canonical wave cw: its tile's base + (cw & 3) * 64 + lane + j * 256
+__device__ inline int ss_canon_item(int cw, int lane, int j) { return (cw >> 2) * 2048 + j * 256 + (cw & 3) * 64 + lane; }
+__device__ inline double ss_canon_wave(double v) {
+    for (int m = 1; m < 64; m <<= 1) v = v + wsmc_bits2d(ss_shfl_xor(wsmc_d2bits(v), m));
+    return v;
+}
+// the total from the canonical waves' totals wv[cw * stride]: each tile's (w0 + w1) + (w2 + w3),
+// then the combine block, whose thread th starts from 0.0 and adds partial th. With at most three
+// partials its butterfly leaves (a0 + a1) + (a2 + a3) in lane 0 after the offsets 1 and 2; the
+// other four offsets and the three idle waves add the zeros they hold
+__device__ inline double ss_canon_total(const double* wv, int stride, int ntiles) {
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    a0 = a0 + ((wv[0] + wv[stride]) + (wv[2 * stride] + wv[3 * stride]));
+    if (ntiles > 1) a1 = a1 + ((wv[4 * stride] + wv[5 * stride]) + (wv[6 * stride] + wv[7 * stride]));
+    if (ntiles > 2) a2 = a2 + ((wv[8 * stride] + wv[9 * stride]) + (wv[10 * stride] + wv[11 * stride]));
+    double r = (a0 + a1) + (a2 + 0.0);
+    for (int m = 4; m < 64; m <<= 1) r = r + 0.0;
+    return (r + 0.0) + (0.0 + 0.0);
+}
+
+// Row t of the moments, at the trace point (before the Resample that follows the step's last
+// OBSERVE): mean[k] and var[k] as wsmc_weighted_moments gives them for expression k = column k
+// alone (z = 0.0 + 1.0 * x) under exp_norm of the weights. Every thread calls it (it holds
+// barriers); thread 0 stores. mean / var: the row's [S] values in global memory, null: not wanted.
+__device__ inline void ss_trace_row(SsState& L, double* mean_out, double* var_out) {
+    const int N = L.N, S = L.S, lane = L.lane, wave = L.wave, nw = L.nw;
+    double* ebuf = L.cb + ss_buf(L, S) * L.stride;   // the spare buffer: free until ss_resample's first barrier
+    double* wv1 = reinterpret_cast<double*>(L.red);  // the scratch is idle before the Resample
+    double* wv2 = wv1 + kSsCanonWaves * kSsTrVals;
+    const int ntiles = (N + 2047) / 2048, ncw = 4 * ntiles;
+
+    // the block max, ss_resample's
+    uint64_t menc = WSMC_ORD_NEG_INF;
+    for (int i = L.i0; i < L.i1; ++i) {
+        const uint64_t e = wsmc_ord_enc(L.lw[i]);
+        menc = e > menc ? e : menc;
+    }
+    for (int m = 32; m >= 1; m >>= 1) {
+        const uint64_t o = ss_shfl_xor(menc, m);
+        menc = o > menc ? o : menc;
+    }
+    if (lane == 0) L.red[wave] = menc;
+    __syncthreads();   // (also: the last Resample's gathers out of the spare's buffer are through)
+    for (int w = 0; w < nw; ++w) menc = L.red[w] > menc ? L.red[w] : menc;
+    const double M = wsmc_ord_dec(menc);   // NaN if any NaN
+    for (int i = L.i0; i < L.i1; ++i) ebuf[i] = wsmc_exp(L.lw[i] - M);
+    __syncthreads();
+
+    // pass 1: S0 = sum e and the sums of e z_k. A unit of work is one canonical wave of one value
+    // (k = -1: e itself), the units dealt over the block's waves
+    for (int u = wave; u < (1 + S) * ncw; u += nw) {
+        const int k = u / ncw - 1, cw = u - (k + 1) * ncw;
+        const double* x = L.cb + ss_buf(L, k < 0 ? 0 : k) * L.stride;
+        double s = 0.0;
+        for (int j = 0; j < 8; ++j) {
+            const int i = ss_canon_item(cw, lane, j);
+            double v = 0.0;
+            if (i < N) v = k < 0 ? ebuf[i] : ebuf[i] * (0.0 + 1.0 * x[i]);
+            s = s + v;
+        }
+        s = ss_canon_wave(s);
+        if (lane == 0) wv1[cw * kSsTrVals + 1 + k] = s;
+    }
+    __syncthreads();
+    // S0 and the means from the waves' totals, where they are used: thread 0 (the row's means) and
+    // the waves that have a unit of pass 2
+    const bool mine = var_out && wave < S * ncw;
+    double S0 = 0.0;
+    if (mine || (wave == 0 && lane == 0)) S0 = ss_canon_total(wv1, kSsTrVals, ntiles);
+    if (mean_out && wave == 0 && lane == 0)
+        for (int k = 0; k < S; ++k) mean_out[k] = ss_canon_total(wv1 + 1 + k, kSsTrVals, ntiles) / S0;
+
+    // pass 2 (a trace with the variances): the sums of (e (z_k - mean_k)) (z_k - mean_k), the same
+    // units; a wave takes the mean of its unit's column from the waves' totals again
+    if (mine)
+        for (int u = wave; u < S * ncw; u += nw) {
+            const int k = u / ncw, cw = u - k * ncw;
+            const double* x = L.cb + ss_buf(L, k) * L.stride;
+            const double m = ss_canon_total(wv1 + 1 + k, kSsTrVals, ntiles) / S0;
+            double s = 0.0;
+            for (int j = 0; j < 8; ++j) {
+                const int i = ss_canon_item(cw, lane, j);
+                double v = 0.0;
+                if (i < N) {
+                    const double z = 0.0 + 1.0 * x[i];
+                    v = (ebuf[i] * (z - m)) * (z - m);
+                }
+                s = s + v;
+            }
+            s = ss_canon_wave(s);
+            if (lane == 0) wv2[cw * WSMC_SSM_MAX_COLS + k] = s;
+        }
+    // with or without pass 2: every read of pass 1's totals (words 0..59 of the scratch) is through
+    // before ss_resample, which the other waves enter next, writes its block max into words 0..15.
+    // Thread 0 then reads pass 2's words 60..107 only, which ss_resample writes behind its first
+    // barrier
+    __syncthreads();
+    if (var_out && wave == 0 && lane == 0)
+        for (int k = 0; k < S; ++k) var_out[k] = ss_canon_total(wv2 + k, WSMC_SSM_MAX_COLS, ntiles) / S0;
 }
 
 // The instantiations by feature set (k_sample<...>'s): a spec without the log-Gamma families

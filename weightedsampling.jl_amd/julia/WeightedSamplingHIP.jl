@@ -900,4 +900,78 @@ function ssm_run_batch(state::HipState, specs, data, n::Integer, seeds::Abstract
             last_ancestors=anc)
 end
 
+# wsmc_ssm_trace (include/wsmc.h): host buffers of the per-step filtering trace, C_NULL for the ones not wanted
+struct WsmcSsmTrace
+    ess::Ptr{Float64}
+    mean::Ptr{Float64}
+    var::Ptr{Float64}
+    log_evidence::Ptr{Float64}
+end
+
+"""
+    ssm_run_traced!(state, spec, data; scheme) -> (log_evidence, trace)
+
+`ssm_run!` with the per-step filtering trace (`wsmc_ssm_run_traced`): `trace.ess` (T), `trace.mean`
+and `trace.var` (n_cols x T, the spec's column order: E[x_t | y_1:t] and the uncorrected variance
+under exp_norm of the weights, what `@E` and `describe` give on an `x{t}` history column) and
+`trace.log_evidence` (T, cumulative; `diff` gives log p(y_t | y_1:t-1)), each taken after step t's
+last observe and before its Resample. Everything else is `ssm_run!`'s. (Written against the C ABI;
+not run in this repository's checks, which have no Julia.)
+"""
+function ssm_run_traced!(state::HipState, spec::WsmcSsmSpec, data::AbstractVecOrMat; scheme=RESAMPLE_STRATIFIED)
+    T = size(data, 1)
+    S = Int(spec.n_cols)
+    d = Vector{Float64}(vec(permutedims(reshape(Float64.(data), T, :))))   # row-major T x data_dim
+    ev = Ref{Float64}(0.0)
+    ess = Vector{Float64}(undef, T); le = Vector{Float64}(undef, T)
+    mean = Matrix{Float64}(undef, S, T); var = Matrix{Float64}(undef, S, T)   # C's [T][n_cols]
+    GC.@preserve ess le mean var begin
+        tr = WsmcSsmTrace(pointer(ess), pointer(mean), pointer(var), pointer(le))
+        check(ccall((:wsmc_ssm_run_traced, libwsmc), Cint,
+                    (Ptr{Cvoid}, Ref{WsmcSsmSpec}, Ptr{Float64}, Int32, Float64, Int32, Ptr{Float64}, Ref{WsmcSsmTrace}),
+                    state.store.ctx, spec, d, T, state.ess_perc_min, scheme, ev, tr))
+    end
+    mirror_flags!(state)
+    return ev[], (ess=ess, mean=mean, var=var, log_evidence=le)
+end
+
+"""
+    ssm_run_batch_traced(state, specs, data, n, seeds; scheme, keep_state=false)
+
+`ssm_run_batch` with every filter's trace (`wsmc_ssm_run_batch_traced`): the named tuple also holds
+`ess` (T x B), `mean` and `var` (n_cols x T x B) and `log_evidence_trace` (T x B). (Written against
+the C ABI; not run in this repository's checks, which have no Julia.)
+"""
+function ssm_run_batch_traced(state::HipState, specs, data, n::Integer, seeds::AbstractVector{<:Integer};
+                              scheme=RESAMPLE_STRATIFIED, keep_state=false)
+    B = length(seeds)
+    sp = specs isa WsmcSsmSpec ? [specs] : collect(WsmcSsmSpec, specs)
+    tabs = data isa AbstractVector{<:AbstractVecOrMat} ? collect(data) : [data]
+    length(sp) in (1, B) && length(tabs) in (1, B) || throw(ArgumentError("one spec / table, or one per filter"))
+    T = size(tabs[1], 1)
+    all(t -> size(t, 1) == T, tabs) || throw(ArgumentError("the filters' tables must have one length"))
+    rowmajor(t) = Vector{Float64}(vec(permutedims(reshape(Float64.(t), T, :))))
+    d = reduce(vcat, rowmajor.(tabs))
+    S = Int(sp[1].n_cols)
+    ev = Vector{Float64}(undef, B); nres = Vector{Int64}(undef, B); last = Vector{Int32}(undef, B)
+    ess = Matrix{Float64}(undef, T, B); le = Matrix{Float64}(undef, T, B)
+    mean = Array{Float64}(undef, S, T, B); var = Array{Float64}(undef, S, T, B)
+    cols = keep_state ? Array{Float64}(undef, n, S, B) : nothing
+    lw = keep_state ? Matrix{Float64}(undef, n, B) : nothing
+    anc = keep_state ? Matrix{Int32}(undef, n, B) : nothing
+    sd = Vector{UInt64}(seeds .% UInt64)
+    GC.@preserve ev nres last ess le mean var cols lw anc begin
+        p(a) = a === nothing ? C_NULL : pointer(a)
+        out = WsmcSsmBatchOut(pointer(ev), C_NULL, p(cols), p(lw), p(anc), pointer(nres), pointer(last))
+        tr = WsmcSsmTrace(pointer(ess), pointer(mean), pointer(var), pointer(le))
+        check(ccall((:wsmc_ssm_run_batch_traced, libwsmc), Cint,
+                    (Ptr{Cvoid}, Ptr{WsmcSsmSpec}, Int32, Ptr{Float64}, Int32, Int32, Int32, Int32, Ptr{UInt64},
+                     Float64, Int32, Ref{WsmcSsmBatchOut}, Ref{WsmcSsmTrace}),
+                    state.store.ctx, sp, length(sp), isempty(d) ? C_NULL : d, length(tabs), T, n, B, sd,
+                    state.ess_perc_min, scheme, out, tr))
+    end
+    return (log_evidence=ev, n_resamples=nres, last_resampled=last .!= 0, ess=ess, mean=mean, var=var,
+            log_evidence_trace=le, cols=cols, log_weights=lw, last_ancestors=anc)
+end
+
 end # module

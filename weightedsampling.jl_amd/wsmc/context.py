@@ -15,7 +15,7 @@ import numpy as np
 
 from . import abi
 from .abi import Dist, Operand, RunTiming, State, check, load_library
-from .ssm import batch_arguments
+from .ssm import SsmTrace, batch_arguments
 
 _D = C.POINTER(C.c_double)
 _I32P = C.POINTER(C.c_int32)
@@ -36,8 +36,10 @@ def _operands4(exprs) -> C.Array:
 class SsmBatchResult:
     """What Context.ssm_run_batch returns: [B] arrays log_evidence, n_resamples, last_resampled;
     ess [B, T] when the trace was asked for; cols (name -> [B, n]), log_weights and last_ancestors
-    [B, n] when the state was (None otherwise)."""
+    [B, n] when the state was (None otherwise); with trace=True also mean and var (name -> [B, T])
+    and log_evidence_trace [B, T], each filter's SsmTrace rows."""
     log_evidence = n_resamples = last_resampled = ess = cols = log_weights = last_ancestors = None
+    mean = var = log_evidence_trace = None
 
 
 class Context:
@@ -466,14 +468,40 @@ class Context:
         check(self._L.wsmc_debug_lgssm(self._h, int(steps), None))
 
     def ssm_run(self, spec, data, ess_perc_min=1.0, scheme: int = abi.RESAMPLE_STRATIFIED,
-                want_evidence: bool = True, ess_trace: bool = False, T: int | None = None):
+                want_evidence: bool = True, ess_trace: bool = False, T: int | None = None, trace=False):
         """A scalar state-space model (wsmc.SSM) as one call (wsmc_ssm_run): the same columns,
         weights, ancestors, state, tape and RNG positions as spec.statements(self, data, ...).
         data: T values, or T rows of the spec's data columns (a spec that reads no data takes T).
         Returns the log evidence (None without want_evidence), or (evidence, trace) with
-        ess_trace: the ESS% of the Resample after each step's last observe."""
+        ess_trace: the ESS% of the Resample after each step's last observe.
+        trace=True (wsmc_ssm_run_traced) returns (evidence, SsmTrace): per step the ESS%, every
+        column's filtered mean and variance and the cumulative log evidence, bit for bit those of
+        spec.statements(self, data, trace=True); everything else the run leaves is the untraced
+        run's. trace may also name the parts wanted: a subset of ("ess", "mean", "var",
+        "log_evidence"); the others are None."""
         tab = spec.table(data, T)
         ev = C.c_double()
+        if trace:
+            if ess_trace:
+                raise ValueError("ess_trace and trace: the trace holds the ESS% (SsmTrace.ess)")
+            parts = ("ess", "mean", "var", "log_evidence") if trace is True else tuple(trace)
+            bad = [p for p in parts if p not in ("ess", "mean", "var", "log_evidence")]
+            if bad:
+                raise ValueError(f"trace: unknown part {bad[0]!r}")
+            steps, S = len(tab), len(spec.cols)
+            buf = {"ess": np.empty(steps), "mean": np.empty((steps, S)), "var": np.empty((steps, S)),
+                   "log_evidence": np.empty(steps)}
+            out = abi.SsmTraceOut()
+            for p in parts:
+                setattr(out, p, _dptr(buf[p]))
+            check(self._L.wsmc_ssm_run_traced(self._h, C.byref(spec.spec), _dptr(tab) if tab.size else None, steps,
+                                              float(ess_perc_min), int(scheme), C.byref(ev) if want_evidence else None,
+                                              C.byref(out)))
+            by_name = lambda a: {c: a[:, k].copy() for k, c in enumerate(spec.cols)}
+            tr = SsmTrace(buf["ess"] if "ess" in parts else None, by_name(buf["mean"]) if "mean" in parts else None,
+                          by_name(buf["var"]) if "var" in parts else None,
+                          buf["log_evidence"] if "log_evidence" in parts else None)
+            return (float(ev.value) if want_evidence else None), tr
         tr = np.empty(len(tab)) if ess_trace else None
         check(self._L.wsmc_ssm_run(self._h, C.byref(spec.spec), _dptr(tab) if tab.size else None, len(tab),
                                    float(ess_perc_min), int(scheme), C.byref(ev) if want_evidence else None,
@@ -497,7 +525,8 @@ class Context:
         check(self._L.wsmc_debug_ssm(self._h, int(steps), None))
 
     def ssm_run_batch(self, specs, data, n: int, seeds, ess_perc_min=1.0, scheme: int = abi.RESAMPLE_STRATIFIED,
-                      ess_trace: bool = False, state: bool = False, T: int | None = None) -> "SsmBatchResult":
+                      ess_trace: bool = False, state: bool = False, T: int | None = None,
+                      trace: bool = False) -> "SsmBatchResult":
         """B = len(seeds) independent filters of n particles in one call (wsmc_ssm_run_batch), one
         persistent workgroup each: filter b is, bit for bit, ssm_run(spec b, table b) on a fresh
         Context(n, seed=seeds[b]). This context gives the device and the stream; its own particles
@@ -506,7 +535,9 @@ class Context:
         data: one table (T values or T rows), or a list / 3-D array of B tables of one length.
         Returns an SsmBatchResult: log_evidence, n_resamples, last_resampled ([B] each), with
         ess_trace `ess` [B, T], with state `cols` (name -> [B, n]), `log_weights` [B, n] and
-        `last_ancestors` [B, n] (row b is zeros while filter b has not resampled)."""
+        `last_ancestors` [B, n] (row b is zeros while filter b has not resampled). trace=True
+        (wsmc_ssm_run_batch_traced) also fills `ess`, `mean` / `var` (name -> [B, T]) and
+        `log_evidence_trace` [B, T]: row b is ssm_run(trace=True)'s SsmTrace of filter b."""
         spec_list, tabs, seeds_a = batch_arguments(specs, data, n, seeds, T)   # (before any device call)
         B, first, steps = len(seeds_a), spec_list[0], len(tabs[0])
         tab = np.ascontiguousarray(np.stack(tabs)) if tabs[0].size else None
@@ -532,9 +563,21 @@ class Context:
             out.cols = _dptr(cols)
             out.log_weights = _dptr(res.log_weights)
             out.last_ancestors = res.last_ancestors.ctypes.data_as(_I32P)
-        check(self._L.wsmc_ssm_run_batch(self._h, arr, len(spec_list), _dptr(tab) if tab is not None else None, len(tabs),
-                                         steps, int(n), B, seeds_a.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                         float(ess_perc_min), int(scheme), C.byref(out)))
+        args = (self._h, arr, len(spec_list), _dptr(tab) if tab is not None else None, len(tabs), steps, int(n), B,
+                seeds_a.ctypes.data_as(C.POINTER(C.c_uint64)), float(ess_perc_min), int(scheme), C.byref(out))
+        if trace:
+            tr = abi.SsmTraceOut()
+            mean, var = np.empty((B, steps, S)), np.empty((B, steps, S))
+            res.log_evidence_trace = np.empty((B, steps))
+            if res.ess is None:
+                res.ess = np.empty((B, steps))
+            tr.ess, tr.mean, tr.var = _dptr(res.ess), _dptr(mean), _dptr(var)
+            tr.log_evidence = _dptr(res.log_evidence_trace)
+            check(self._L.wsmc_ssm_run_batch_traced(*args, C.byref(tr)))
+            res.mean = {name: mean[:, :, k].copy() for k, name in enumerate(first.cols)}
+            res.var = {name: var[:, :, k].copy() for k, name in enumerate(first.cols)}
+        else:
+            check(self._L.wsmc_ssm_run_batch(*args))
         res.last_resampled = res.last_resampled.astype(bool)
         if state:
             res.cols = {name: cols[:, k, :] for k, name in enumerate(first.cols)}

@@ -76,6 +76,21 @@ def batch_arguments(specs, data, n, seeds, T=None):
     return spec_list, tabs, seeds_a
 
 
+class SsmTrace:
+    """The per-step filtering trace of a scalar-SSM run (include/wsmc.h wsmc_ssm_trace). Row t is
+    taken after step t's last observe, before the Resample that follows it: `ess` [T] that
+    Resample's ESS%; `mean` / `var` (column name -> [T]) E[x_t | y_1:t] and the uncorrected
+    variance under exp_norm of the weights (Context.weighted_moments of the column alone);
+    `log_evidence` [T], cumulative (its first difference is log p(y_t | y_1:t-1))."""
+
+    def __init__(self, ess, mean, var, log_evidence):
+        self.ess, self.mean, self.var, self.log_evidence = ess, mean, var, log_evidence
+
+    def predictive_loglik(self) -> np.ndarray:
+        """log p(y_t | y_1:t-1), t = 0 .. T-1: the first difference of log_evidence"""
+        return np.diff(self.log_evidence, prepend=0.0)
+
+
 class SSM:
     """A builder for wsmc_ssm_spec: SSM(cols=[...]).init(...).step(...)."""
 
@@ -202,13 +217,18 @@ class SSM:
 
     # ---- the executable definition ----
     def statements(self, backend, data, ess_perc_min: float = 1.0, scheme: int = abi.RESAMPLE_STRATIFIED,
-                   wait: bool = True, T: int | None = None):
+                   wait: bool = True, T: int | None = None, trace: bool = False):
         """Issue the spec's statements one by one on `backend` (a Context or the tests' Oracle: any
         object with the operator methods), each `sample` / `observe` followed by its Resample, the
         step's data folded into constants: a data slot of an operand is removed and its value
         becomes c0, a data read of a program becomes a constant. This is what wsmc_ssm_run
         computes. wait=True returns (flags, ESS%) of the Resample after each step's last observe;
-        wait=False leaves every Resample asynchronous and returns None."""
+        wait=False leaves every Resample asynchronous and returns None. trace=True (with wait)
+        also takes backend.weighted_moments of every column and backend.log_evidence() between each
+        step's last observe and its Resample and returns (flags, ESS%, SsmTrace): the definition
+        of what Context.ssm_run(trace=True) returns."""
+        if trace and not wait:
+            raise ValueError("trace=True needs wait=True (the trace point is a synchronisation)")
         sp = self.spec
         tab = self.table(data, T)
         T = len(tab)
@@ -273,8 +293,10 @@ class SSM:
                 d = fold_dist(s.dist, patch)
                 x = [fold_operand(s.value, patch)]
 
-                def call(waited):
+                def call(waited, at=None):
                     backend.observe(d, x)
+                    if at is not None:
+                        at()
                     return backend.resample(ess_perc_min, scheme, wait=waited)
             return call, patch
 
@@ -283,13 +305,30 @@ class SSM:
         last = max(q for q in range(sp.n_step) if sp.step[q].kind == abi.SSM_OBSERVE)
         step = [prepare(sp.step[q]) for q in range(sp.n_step)]
         flags, ess = [], []
+        if trace:
+            S = len(self.cols)
+            mean, var, lev = np.empty((T, S)), np.empty((T, S)), np.empty(T)
+            exprs = [Operand.column(ids[k]) for k in range(S)]
+
+        def point(t):
+            m, cv = backend.weighted_moments(exprs)
+            mean[t], var[t] = m, np.diagonal(cv)
+            lev[t] = backend.log_evidence()
+
         for t in range(T):
             row = tab[t]
             for q, (call, patch) in enumerate(step):
                 for obj, field, j in patch:
                     setattr(obj, field, row[j])
-                r = call(wait and q == last)
+                if trace and q == last:
+                    r = call(True, lambda: point(t))
+                else:
+                    r = call(wait and q == last)
                 if wait and q == last:
                     flags.append(bool(r[0]))
                     ess.append(float(r[1]))
+        if trace:
+            tr = SsmTrace(np.array(ess), {c: mean[:, k].copy() for k, c in enumerate(self.cols)},
+                          {c: var[:, k].copy() for k, c in enumerate(self.cols)}, lev)
+            return flags, tr.ess, tr
         return (flags, np.array(ess)) if wait else None
