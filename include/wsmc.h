@@ -405,7 +405,11 @@ int wsmc_last_ancestors(wsmc_ctx* ctx, int32_t* host);
  *   v .= v + dv; o_t => MvNormal(x{t+1}, r_var I)   (+ the auto-inserted Resamples)
  * Columns created: x_1 .. x_{T+1} (dim 2, when keep_history), x (dim 2, otherwise), v, dv.
  * Produces the same columns, weights and RNG stream positions as issuing the same
- * statements one by one through the operators above.                                   */
+ * statements one by one through the operators above.
+ * The fused kernels write these columns and no other. A context that holds any other column (an
+ * earlier, longer run's x_{T+2} .., the other store mode's, the caller's own) gets the same
+ * statements issued one by one through the operators above instead, whose Resamples gather
+ * every column of the store (wsmc_debug_ssm2d_routes counts the two routes).             */
 int wsmc_ssm2d_run(wsmc_ctx* ctx, const double* obs /* T x 2, row-major */, int32_t T,
                    const double* x0, const double* v0, double q_var, double r_var,
                    double ess_perc_min, int32_t scheme, int32_t keep_history,
@@ -656,6 +660,10 @@ int wsmc_debug_run_stats(wsmc_ctx* ctx, int64_t* stats_out);
  * only when step t - 1 did not resample or t is the last step; every other layout stores every
  * row. stats_out holds 4 values. */
 int wsmc_debug_weight_stores(wsmc_ctx* ctx, int64_t* stats_out);
+/* wsmc_ssm2d_run's calls by route, cumulative (a sharded handle reports its first shard):
+ * stats_out[0] = the fused runs, stats_out[1] = the runs issued as statements because the context
+ * held a column that is not the run's. stats_out holds 2 values. */
+int wsmc_debug_ssm2d_routes(wsmc_ctx* ctx, int64_t* stats_out);
 
 #ifdef __cplusplus
 }

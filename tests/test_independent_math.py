@@ -185,17 +185,20 @@ def checked_move(ctx, targets, fold, n, min_step=1e-3, lo=None, hi=None, proposa
 # ---------------------------------------------------------------------------------------
 # (a) the 2D SSM step
 # ---------------------------------------------------------------------------------------
-def run_ssm2d_checked(backend, n, T, ess_min, scheme=wsmc.RESAMPLE_STRATIFIED):
+def run_ssm2d_checked(backend, n, T, ess_min, scheme=wsmc.RESAMPLE_STRATIFIED, obs=None, x0=(0.0, 0.0),
+                      v0=(1.0, 0.0), q_var=0.1, r_var=0.5):
+    """obs: the observations (default: the model's own data, ssm2d_data(T)); q_var and r_var are
+    variances here by this file's own arithmetic (sqrt(q_var) z, the density over r_var I), whatever
+    the shared headers do with them."""
     ctx = make_ctx(backend, n, seed=SEED)
     Rz = resolver(ctx)
-    obs = ssm2d_data(T)
-    q_var, r_var = 0.1, 0.5
+    obs = ssm2d_data(T) if obs is None else np.asarray(obs, dtype=float).reshape(T, 2)
     I2 = np.eye(2)
     idx = np.arange(n, dtype=np.uint64)
     cx1 = ctx.col_create("x_1", 2)
-    ctx.assign(cx1, _const((0.0, 0.0)))
+    ctx.assign(cx1, _const(x0))
     cv = ctx.col_create("v", 2)
-    ctx.assign(cv, _const((1.0, 0.0)))
+    ctx.assign(cv, _const(v0))
     dv_dist = MvNormal([0.0, 0.0], q_var * I2).dist(Rz)
     cdv, n_rs = -1, 0
     for t, o in enumerate(obs, start=1):

@@ -4509,8 +4509,92 @@ static void run_book(wsmc_ctx* c, const RunPlan& p, const double* obs);
 static void run_fold_decisions(wsmc_ctx* c, const Decision* hdec, int T);
 static int fold_run(wsmc_ctx* c, RunPend* P, RunPend* Q);
 
+// The fused run writes the model's own columns and nothing else, so its Resamples never reach a
+// column the context holds besides them: an earlier, longer run's x_{T+2} .., the columns of a run
+// in the other store mode, a caller's own. The statements' Resamples gather every column of the
+// store (src/stores.jl:105-128), so such a context takes the statement route: the same model
+// through the operators one by one, which is the definition of the run's result (as wsmc_ssm_run
+// does with a column that is not its spec's). Any handle, any scheme.
+static bool ssm2d_own_column(const std::string& nm, int T, bool keep) {
+    if (nm == "v" || nm == "dv") return true;
+    if (!keep) return nm == "x";
+    if (nm.size() < 3 || nm.compare(0, 2, "x_") != 0 || nm[2] == '0') return false;
+    int64_t k = 0;
+    for (size_t i = 2; i < nm.size(); ++i) {
+        if (nm[i] < '0' || nm[i] > '9') return false;
+        k = k * 10 + (nm[i] - '0');
+        if (k > (int64_t)T + 1) return false;
+    }
+    return true;
+}
+static wsmc_operand const_operand(double v) {
+    wsmc_operand r;
+    std::memset(&r, 0, sizeof(r));
+    r.c0 = v;
+    r.col[0] = r.col[1] = -1;
+    return r;
+}
+static wsmc_dist ssm2d_iso(int32_t mean_col, double var) {
+    wsmc_dist d;
+    std::memset(&d, 0, sizeof(d));
+    d.family = WSMC_FAM_MVNORMAL_ISO;
+    d.mean_fn = WSMC_MEAN_AFFINE;
+    d.dim = 2;
+    for (int k = 0; k < 4; ++k) d.mu[k] = mean_col >= 0 && k < 2 ? col_operand(mean_col, k) : const_operand(0.0);
+    d.scale = const_operand(var);
+    return d;
+}
+static int ssm2d_statements(wsmc_ctx* c, const double* obs, int32_t T, const double* x0, const double* v0, double q_var,
+                            double r_var, double ess_min, int32_t scheme, bool keep, double* log_evidence_out) {
+    int rc;
+    int32_t cx = -1, cv = -1, cdv = -1;
+    wsmc_operand e[4];
+    if ((rc = wsmc_col_create(c, keep ? "x_1" : "x", 2, &cx))) return rc;
+    for (int k = 0; k < 4; ++k) e[k] = const_operand(k < 2 ? x0[k] : 0.0);
+    if ((rc = wsmc_assign(c, cx, e))) return rc;                                  // x{1} .= x0
+    if ((rc = wsmc_col_create(c, "v", 2, &cv))) return rc;
+    for (int k = 0; k < 4; ++k) e[k] = const_operand(k < 2 ? v0[k] : 0.0);
+    if ((rc = wsmc_assign(c, cv, e))) return rc;                                  // v .= v0
+    const wsmc_dist dvd = ssm2d_iso(-1, q_var);
+    for (int t = 1; t <= T; ++t) {
+        int32_t cxn = cx;
+        if (keep && (rc = wsmc_col_create(c, ("x_" + std::to_string(t + 1)).c_str(), 2, &cxn))) return rc;
+        if (t == 1 && (rc = wsmc_col_create(c, "dv", 2, &cdv))) return rc;
+        for (int k = 0; k < 4; ++k) {
+            e[k] = k < 2 ? col_operand(cx, k) : const_operand(0.0);
+            if (k < 2) { e[k].col[1] = cv; e[k].comp[1] = k; e[k].coef[1] = 1.0; }
+        }
+        if ((rc = wsmc_assign(c, cxn, e))) return rc;                             // x{t+1} .= x{t} + v
+        if ((rc = wsmc_sample(c, cdv, &dvd))) return rc;                          // dv ~ MvNormal(0, q_var I)
+        if ((rc = wsmc_resample(c, ess_min, scheme, nullptr, nullptr))) return rc;
+        for (int k = 0; k < 4; ++k) {
+            e[k] = k < 2 ? col_operand(cv, k) : const_operand(0.0);
+            if (k < 2) { e[k].col[1] = cdv; e[k].comp[1] = k; e[k].coef[1] = 1.0; }
+        }
+        if ((rc = wsmc_assign(c, cv, e))) return rc;                              // v .= v + dv
+        const wsmc_dist od = ssm2d_iso(cxn, r_var);
+        for (int k = 0; k < 4; ++k) e[k] = const_operand(k < 2 ? obs[2 * (t - 1) + k] : 0.0);
+        if ((rc = wsmc_observe(c, &od, e))) return rc;                            // o_t => MvNormal(x{t+1}, r_var I)
+        if ((rc = wsmc_resample(c, ess_min, scheme, nullptr, nullptr))) return rc;
+        cx = cxn;
+    }
+    return log_evidence_out ? wsmc_log_evidence(c, log_evidence_out) : WSMC_OK;
+}
+
 int wsmc_ssm2d_run(wsmc_ctx* c, const double* obs, int32_t T, const double* x0, const double* v0, double q_var,
                    double r_var, double ess_min, int32_t scheme, int32_t keep_history, double* log_evidence_out) {
+    if (c && obs && T >= 1 && x0 && v0 && valid_scheme(scheme) && q_var > 0 && r_var > 0) {
+        wsmc_ctx* h = c->multi ? multi_first(c) : c;   // (every shard holds the same columns; the counters' holder)
+        bool foreign = false;
+        for (const auto& col : h->cols) foreign |= !ssm2d_own_column(col.name, T, keep_history != 0);
+        if (foreign && !(exact_mode(h) && scheme == WSMC_RESAMPLE_MULTINOMIAL)) {   // (that pair is refused below)
+            const int rc = ssm2d_statements(c, obs, T, x0, v0, q_var, r_var, ess_min, scheme, keep_history != 0,
+                                            log_evidence_out);
+            if (!rc) h->run_stmt_runs += 1;
+            return rc;
+        }
+        if (!c->multi) c->run_fused_runs += 1;   // (a handle over shards: each shard's own call counts)
+    }
     if (c && c->multi)
         return multi_each(c, [&](wsmc_ctx* x) {
             double ev = 0;
@@ -6031,6 +6115,14 @@ int wsmc_debug_run_stats(wsmc_ctx* c, int64_t* stats_out) {
     stats_out[1] = run_qstat_mode(c->N);
     stats_out[2] = c->run_replays;
     stats_out[3] = c->rs_qs_batches;
+    return WSMC_OK;
+}
+
+int wsmc_debug_ssm2d_routes(wsmc_ctx* c, int64_t* stats_out) {
+    if (c && c->multi) return wsmc_debug_ssm2d_routes(multi_first(c), stats_out);
+    if (!c || !stats_out) return fail(WSMC_EARG, "null argument");
+    stats_out[0] = c->run_fused_runs;
+    stats_out[1] = c->run_stmt_runs;
     return WSMC_OK;
 }
 

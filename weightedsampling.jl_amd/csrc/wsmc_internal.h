@@ -362,6 +362,7 @@ struct wsmc_ctx {
                                             // (bits) and observations, read by the run's head kernel
     hipEvent_t run_ev[2] = {nullptr, nullptr};   // recorded behind each parity's read-back
     int64_t run_missed = 0, run_replays = 0; // single GPU: steps whose guess missed, runs re-done
+    int64_t run_fused_runs = 0, run_stmt_runs = 0;   // wsmc_ssm2d_run calls by route (wsmc_debug_ssm2d_routes)
     wsmc::ShardRecord* run_rec = nullptr;   // [(T+1) * world]
     wsmc::Decision* run_dec = nullptr;      // [T+1]
     int32_t* anc_log = nullptr;             // [T][N]

@@ -222,6 +222,7 @@ SIGNATURES = {
     "wsmc_debug_mv_jit_selfcheck": (C.c_int, []),
     "wsmc_debug_run_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "wsmc_debug_weight_stores": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "wsmc_debug_ssm2d_routes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "wsmc_comm_set_timeout": (C.c_int, [C.c_void_p, C.c_double]),
 }
 

@@ -425,6 +425,13 @@ class Context:
         check(self._L.wsmc_debug_weight_stores(self._h, st))
         return {"stored": st[0], "recomputed": st[1], "qs_launches": st[2], "plain_launches": st[3]}
 
+    def ssm2d_routes(self) -> dict:
+        """ssm2d_run's calls by route (wsmc_debug_ssm2d_routes, cumulative): the fused runs, and the
+        runs issued as statements because the context held a column that is not the run's."""
+        st = (C.c_int64 * 2)()
+        check(self._L.wsmc_debug_ssm2d_routes(self._h, st))
+        return {"fused_runs": st[0], "statement_runs": st[1]}
+
     def ssm2d_run(self, obs, x0=(0.0, 0.0), v0=(1.0, 0.0), q_var=0.1, r_var=0.5, ess_perc_min=0.5,
                   scheme: int = abi.RESAMPLE_STRATIFIED, keep_history: bool = True,
                   want_evidence: bool = True):
