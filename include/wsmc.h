@@ -588,6 +588,55 @@ int wsmc_ssm_run_batch_traced(wsmc_ctx* ctx, const wsmc_ssm_spec* specs, int32_t
                               const double* data, int32_t n_tables, int32_t T, int32_t n, int32_t B,
                               const uint64_t* seeds, double ess_perc_min, int32_t scheme,
                               wsmc_ssm_batch_out* out, const wsmc_ssm_trace* trace);
+/* ---- sampled trajectories and smoothed moments from the two runs above -----------------------
+ * The genealogy of the final particles, traced back through every resampling step of the run:
+ * paths[t][k][i] is column k at trace point t (the filtering trace's: after step t's last OBSERVE,
+ * before the Resample that follows it) of final particle i's ancestor; mean[t][k] and var[t][k]
+ * are wsmc_weighted_moments of row t (d = n_cols, expression k = paths[t][k] alone) under the
+ * final weights, so E[x_t | y_1:T] and the uncorrected variance of the genealogy's estimate. Bit
+ * for bit what the statements issued one by one give when every column is copied at each trace
+ * point into a column of its own, which the Resamples that follow gather like any other. A row
+ * of paths picked by exp_norm of the final weights is a draw from the smoothing distribution.
+ * Caller-owned host buffers, each may be NULL (not wanted). */
+typedef struct {
+    double* paths;              /* [T][n_cols][n]   (batch: [B][T][n_cols][n]) */
+    double* mean;               /* [T][n_cols]      (batch: [B][T][n_cols])    */
+    double* var;                /* [T][n_cols]      (batch: [B][T][n_cols])    */
+} wsmc_ssm_smooth;
+/* sizeof(wsmc_ssm_smooth) as the library was built (layout check) */
+int wsmc_ssm_smooth_sizeof(int64_t* bytes);
+/* wsmc_ssm_run_traced with the smoothed output. The persistent workgroup stores its columns at
+ * every trace point and its ancestors after every Resample that ran to device memory; after the
+ * last step one kernel follows every final particle's ancestors back through the log and a second
+ * gathers the rows and takes their moments: O(T n) work, no host round trip per step. Everything
+ * else the run leaves (columns, weights, ancestors, state fields, tape, evidence, RNG positions,
+ * wsmc_debug_ssm's routes, the filtering trace if asked) is bit for bit wsmc_ssm_run_traced's, and
+ * the particle caps are the same (the history is not in LDS).
+ * The call has the persistent route only (the store could not drop the T n_cols columns the
+ * statements would leave): WSMC_EARG, with the reason in wsmc_last_error() and the context as it
+ * was, for n above the cap of the column count, a column that is not the spec's, multinomial
+ * resampling, a sharded or multi-device handle, weights_changed set, more than WSMC_XPROG_MAX
+ * program instructions. smooth NULL, or every member NULL: wsmc_ssm_run_traced.
+ * The call allocates, for its duration, 8 T n n_cols bytes for the history, 4 T n n_obs for the
+ * ancestor log (n_obs: the OBSERVEs of a step) and 16 T n_cols + 4 T n_obs for the rows and the
+ * log's flags; WSMC_ENOMEM (the context as it was) when the device refuses them. */
+int wsmc_ssm_run_smoothed(wsmc_ctx* ctx, const wsmc_ssm_spec* spec, const double* data, int32_t T,
+                          double ess_perc_min, int32_t scheme, double* log_evidence_out,
+                          const wsmc_ssm_trace* trace, const wsmc_ssm_smooth* smooth);
+/* wsmc_ssm_run_batch_traced with the smoothed output of every filter (row b of each array is what
+ * wsmc_ssm_run_smoothed gives on a fresh wsmc_create(n, seeds[b]) context); the same refusals as
+ * wsmc_ssm_run_batch. The bytes above, per filter, are part of the call's device allocation;
+ * WSMC_ENOMEM when the device refuses it. smooth NULL, or every member NULL:
+ * wsmc_ssm_run_batch_traced. */
+int wsmc_ssm_run_batch_smoothed(wsmc_ctx* ctx, const wsmc_ssm_spec* specs, int32_t n_specs,
+                                const double* data, int32_t n_tables, int32_t T, int32_t n, int32_t B,
+                                const uint64_t* seeds, double ess_perc_min, int32_t scheme,
+                                wsmc_ssm_batch_out* out, const wsmc_ssm_trace* trace,
+                                const wsmc_ssm_smooth* smooth);
+/* stats_out[4] = the last smoothed run or batch on ctx: device time (HIP events on the stream) of its
+ * segments, of the trace-back (phase 1) and of the rows kernel (phase 2), microseconds, and the
+ * bytes the call allocated for the log and the rows. */
+int wsmc_debug_ssm_smooth(wsmc_ctx* ctx, int64_t* stats_out);
 /* per-kernel timing of the last fused run (HIP events on the ctx stream), ms */
 typedef struct {
     double total_ms;            /* whole run, first kernel to last                       */

@@ -25,7 +25,19 @@ bench.py stays the headline.
 
 The trace leg (wsmc_ssm_run_traced): the persistent run untraced, traced, and the only other way to
 the same rows, spec.statements(ctx, data, trace=True), which waits at every step. Same protocol
-(the statements' warm-up is at most 1000 steps long); lines go to profiles/ssm_trace.jsonl."""
+(the statements' warm-up is at most 1000 steps long); lines go to profiles/ssm_trace.jsonl.
+
+    python tools/bench_ssm.py --smooth                   sv and lgssm at T = 1e3, 1e4
+    python tools/bench_ssm.py --smooth --leg sv --T 1000
+
+The smooth leg (wsmc_ssm_run_smoothed), forced resampling: the persistent run untraced, smoothed
+asking for the moments only, smoothed asking for moments and paths, and at T = 1e3 (T n_cols must
+stay under the store's 4096 columns) the only other way to the same rows, spec.statements(ctx, data,
+smooth=True) on a Context with the lazy store. The routes alternate inside a round; a round runs
+each route on fresh contexts (made before the clock starts) as often as fills half a second; the
+figure is the median over three rounds after a warm-up round, with the rounds' range beside it.
+The device times of the trace-back's two kernels are the library's own (HIP events,
+Context.ssm_smooth_stats). Lines go to profiles/ssm_smooth.jsonl."""
 import argparse
 import json
 import pathlib
@@ -40,6 +52,7 @@ N = 1000
 LEGS = ["sv", "poisson_count", "kitagawa", "local_trend", "lgssm"]
 OUT = ROOT / "profiles" / "ssm_fused.jsonl"
 OUT_TRACE = ROOT / "profiles" / "ssm_trace.jsonl"
+OUT_SMOOTH = ROOT / "profiles" / "ssm_smooth.jsonl"
 
 
 def best_of(run, reps=2):
@@ -176,8 +189,90 @@ def child_trace(leg: str, T: int) -> dict:
             "factor_vs_statements_traced": s / p, "log_evidence": ev}
 
 
-def driver(Ts, legs, trace=False) -> int:
-    out = OUT_TRACE if trace else OUT
+def child_smooth(leg: str, T: int) -> dict:
+    import statistics
+    import numpy as np
+    import wsmc
+    from wsmc import models
+    if leg == "lgssm":
+        spec, data = models.lgssm1d_spec(), models.lgssm1d_data(T)
+    else:
+        make, gen = models.SSM_MODELS[leg]
+        spec, data = make(), gen(T)
+    S = len(spec.cols)
+    last = {}
+
+    def fused(smooth):
+        def run(ctx):
+            r = ctx.ssm_run(spec, data, ess_perc_min=1.0, smooth=smooth)
+            assert ctx.ssm_stats()["persistent_runs"] == 1
+            if smooth:
+                last[smooth if smooth is True else "moments"] = (r, ctx.ssm_smooth_stats())
+            else:
+                last["untraced"] = (r, None)
+        return run
+
+    def statements(ctx):
+        ctx.store_set_lazy(True)
+        r = spec.statements(ctx, data, ess_perc_min=1.0, smooth=True)
+        last["statements"] = ((ctx.log_evidence(), r[2]), None)
+
+    routes = {"untraced": fused(False), "moments": fused(("mean", "var")), "paths": fused(True)}
+    if T * S + S <= 4096:
+        routes["statements"] = statements
+    times = {k: [] for k in routes}
+    reps = {k: 1 for k in routes}
+    for rnd in range(5):   # round 0 warms up, round 1 sizes the windows, rounds 2..4 are the figures
+        for name, run in routes.items():
+            ctxs = [wsmc.Context(N, seed=42) for _ in range(reps[name])]
+            for c in ctxs:
+                c.sync()
+            t0 = time.perf_counter()
+            for c in ctxs:
+                run(c)
+            dt = (time.perf_counter() - t0) / len(ctxs)
+            for c in ctxs:
+                c.close()
+            if rnd == 1:
+                reps[name] = max(1, min(64, int(0.5 / dt) + 1))
+            if rnd >= 2:
+                times[name].append(dt)
+    last["paths"] = last.pop(True)
+    med = {k: statistics.median(v) for k, v in times.items()}
+    same = lambda a, b: bool(((a.view(np.uint64) == b.view(np.uint64)) | (np.isnan(a) & np.isnan(b))).all())
+    (ev_p, sm_p), st_p = last["paths"]
+    (ev_m, sm_m), st_m = last["moments"]
+    assert last["untraced"][0] == ev_p == ev_m
+    assert all(same(sm_p.mean[c], sm_m.mean[c]) and same(sm_p.var[c], sm_m.var[c]) for c in spec.cols)
+    out = {"leg": leg, "N": N, "T": T, "columns": S, "step_statements": spec.spec.n_step, "runs_per_round": reps,
+           "log_evidence": ev_p, "log_bytes": st_p["log_bytes"]}
+    for k in routes:
+        out[f"{k}_s"] = med[k]
+        out[f"{k}_s_range"] = [min(times[k]), max(times[k])]
+        out[f"{k}_us_per_step"] = 1e6 * med[k] / T
+    tb = st_m["traceback_s"] + st_m["rows_s"]
+    out.update(segments_device_s=st_m["segments_s"], traceback_device_s=st_m["traceback_s"], rows_device_s=st_m["rows_s"],
+               rows_with_paths_device_s=st_p["rows_s"],
+               # (a) what the smoothed call adds to a step beyond the two trace-back kernels: the recording
+               # stores, the traced instantiation, the allocation and the flags' memset
+               recording_us_per_step=1e6 * (med["moments"] - med["untraced"] - tb) / T,
+               recording_device_us_per_step=1e6 * (st_m["segments_s"] - med["untraced"]) / T,
+               # (b) the trace-back's device time per step and particle, both kernels
+               traceback_ns_per_step_particle=1e9 * tb / (T * N),
+               smoothing_share_of_moments_call=(med["moments"] - med["untraced"]) / med["moments"])
+    if "statements" in routes:
+        (ev_s, sm_s), _ = last["statements"]
+        assert ev_s == ev_p
+        assert all(same(sm_p.mean[c], sm_s.mean[c]) and same(sm_p.var[c], sm_s.var[c]) and same(sm_p.paths[c], sm_s.paths[c])
+                   for c in spec.cols)
+        # (c) the speed-up over the only alternative
+        out.update(factor_vs_statements_moments=med["statements"] / med["moments"],
+                   factor_vs_statements_paths=med["statements"] / med["paths"])
+    return out
+
+
+def driver(Ts, legs, trace=False, smooth=False) -> int:
+    out = OUT_SMOOTH if smooth else OUT_TRACE if trace else OUT
     OUT.parent.mkdir(exist_ok=True)
     for leg in legs:
         per_step = None   # seconds a step of one child (all its routes and repetitions), from the run before
@@ -185,6 +280,7 @@ def driver(Ts, legs, trace=False) -> int:
             limit = 180 if per_step is None else int(60 + 3 * per_step * T)
             cmd = ["timeout", "-k", "10", str(limit), sys.executable, __file__, "--leg", leg, "--T", str(T)]
             cmd += ["--trace"] if trace else []
+            cmd += ["--smooth"] if smooth else []
             t0 = time.perf_counter()
             r = subprocess.run(cmd, capture_output=True, text=True)
             dt = time.perf_counter() - t0
@@ -206,10 +302,13 @@ if __name__ == "__main__":
     ap.add_argument("--T", type=int, action="append")
     ap.add_argument("--legs", default=",".join(LEGS))
     ap.add_argument("--trace", action="store_true", help="the trace leg (profiles/ssm_trace.jsonl)")
+    ap.add_argument("--smooth", action="store_true", help="the smooth leg (profiles/ssm_smooth.jsonl)")
     a = ap.parse_args()
     if a.leg:
-        print(json.dumps((child_trace if a.trace else child)(a.leg, (a.T or [1000])[0])), flush=True)
+        print(json.dumps((child_smooth if a.smooth else child_trace if a.trace else child)(a.leg, (a.T or [1000])[0])), flush=True)
         sys.exit(0)
+    if a.smooth:
+        sys.exit(driver(a.T or [1000, 10_000], a.legs.split(",") if a.legs != ",".join(LEGS) else ["sv", "lgssm"], smooth=True))
     if a.trace:
         sys.exit(driver(a.T or [10_000, 100_000], a.legs.split(","), trace=True))
     sys.exit(driver(a.T or [1000, 10_000, 100_000], a.legs.split(",")))

@@ -20,6 +20,11 @@ fails, or runs into its limit, ends the driver: nothing more is started on the d
             traced call, and the device memory the trace takes, B T (2 S + 2) 8 bytes. Lines go to
             profiles/ssm_trace.jsonl.
 
+  --smooth  (with --leg batch) the same call untraced and smoothed, asking for the moments only
+            (wsmc_ssm_run_batch_smoothed), alternating in one process, T = 1e3 by default: seconds of
+            both, the device times of the trace-back's two kernels and the bytes of the log. Lines go
+            to profiles/ssm_smooth.jsonl.
+
 `ratio` is batch seconds over the baseline scaled to B; the bar is ratio < 1/16 at B = CU count
 (16 is the number of processes that may hold the device at once: the only other way to fill it).
 One JSON line per child, appended to profiles/ssm_batch.jsonl (--out). Diagnostics for DESIGN.md
@@ -91,6 +96,35 @@ def batch_traced(T: int, B: int) -> dict:
     S = len(specs[0].cols)
     return {"leg": "batch_traced", "n": N, "T": T, "B": B, "untraced_s": best[False], "traced_s": best[True],
             "trace_share": (best[True] - best[False]) / best[True], "trace_device_bytes": B * T * (2 * S + 2) * 8,
+            "blocks_per_cu": st["blocks_per_cu"], "cus": st["cus"], "segments": st["segments"]}
+
+
+def batch_smoothed(T: int, B: int) -> dict:
+    import statistics
+    import wsmc
+    from wsmc import models
+    data = models.sv_data(T)
+    specs, seeds = filters(B)
+    ctx = wsmc.Context(1, seed=1)
+    times = {False: [], True: []}
+    res = {}
+    for rep in range(8):   # the first round warms up; then the median of 7, the two calls alternating
+        for smooth in (False, True):
+            t0 = time.perf_counter()
+            res[smooth] = ctx.ssm_run_batch(specs, data, N, seeds, ess_perc_min=1.0, smooth=("mean", "var") if smooth else False)
+            dt = time.perf_counter() - t0
+            if rep > 0:
+                times[smooth].append(dt)
+    st, sm = ctx.ssm_batch_stats(), ctx.ssm_smooth_stats()
+    assert (res[True].log_evidence == res[False].log_evidence).all() and (res[True].n_resamples == T).all()
+    assert res[True].smean["h"].shape == (B, T) and res[True].paths is None
+    ctx.close()
+    u, s = statistics.median(times[False]), statistics.median(times[True])
+    return {"leg": "batch_smoothed", "n": N, "T": T, "B": B, "untraced_s": u, "untraced_s_range": [min(times[False]), max(times[False])],
+            "smoothed_moments_s": s, "smoothed_moments_s_range": [min(times[True]), max(times[True])],
+            "filter_steps_per_s": B * T / s,
+            "segments_device_s": sm["segments_s"], "traceback_device_s": sm["traceback_s"], "rows_device_s": sm["rows_s"],
+            "traceback_ns_per_step_particle": 1e9 * (sm["traceback_s"] + sm["rows_s"]) / (B * T * N), "log_bytes": sm["log_bytes"],
             "blocks_per_cu": st["blocks_per_cu"], "cus": st["cus"], "segments": st["segments"]}
 
 
@@ -175,11 +209,14 @@ if __name__ == "__main__":
     ap.add_argument("--ev0", type=float, default=None)
     ap.add_argument("--out", type=pathlib.Path, default=OUT)
     ap.add_argument("--trace", action="store_true", help="with --leg batch: untraced against traced")
+    ap.add_argument("--smooth", action="store_true", help="with --leg batch: untraced against smoothed (moments only)")
     a = ap.parse_args()
     if a.leg == "probe":
         print(json.dumps(probe()), flush=True)
     elif a.leg == "baseline":
         print(json.dumps(baseline(a.T)), flush=True)
+    elif a.leg == "batch" and a.smooth:
+        print(json.dumps(batch_smoothed(a.T, a.B)), flush=True)
     elif a.leg == "batch" and a.trace:
         print(json.dumps(batch_traced(a.T, a.B)), flush=True)
     elif a.leg == "batch":

@@ -5606,9 +5606,88 @@ int wsmc_ssm_trace_sizeof(int64_t* bytes) {
     return WSMC_OK;
 }
 
-// wsmc_ssm_run and wsmc_ssm_run_traced: tr's members are null where nothing is wanted
+int wsmc_ssm_smooth_sizeof(int64_t* bytes) {
+    if (!bytes) return fail(WSMC_EARG, "null argument");
+    *bytes = (int64_t)sizeof(wsmc_ssm_smooth);
+    return WSMC_OK;
+}
+
+// a call's device allocation, freed on return (hipFree waits for the device)
+struct SsmSlab {
+    char* p = nullptr;
+    ~SsmSlab() { if (p) (void)hipFree(p); }
+};
+static size_t ssm_up(size_t v) { return (v + 255) & ~(size_t)255; }
+static int ssm_count_observes(const wsmc_ssm_spec* sp) {
+    int n = 0;
+    for (int q = 0; q < sp->n_step; ++q) n += sp->step[q].kind == WSMC_SSM_OBSERVE;
+    return n;
+}
+// A smoothed run's log for B filters of n particles, carved from `base` (null: the sizes alone):
+// the history, the ancestor log, its flags, then the smoothed rows where wanted. Returns the bytes
+struct SsmSmoothBufs {
+    SsmRec rec;
+    double *mean, *var;
+    size_t flags_off, flags_bytes;   // the flags (zeroed before the run)
+};
+static size_t ssm_smooth_carve(char* base, const wsmc_ssm_smooth& sm, int64_t B, int64_t T, int64_t n, int S, int n_obs,
+                               SsmSmoothBufs* out) {
+    const size_t nhist = ssm_up(sizeof(double) * (size_t)B * T * S * n), nlog = ssm_up(sizeof(int32_t) * (size_t)B * T * n_obs * n),
+                 nflag = ssm_up(sizeof(int32_t) * (size_t)B * T * n_obs), nrow = ssm_up(sizeof(double) * (size_t)B * T * S);
+    if (out) {
+        char* q = base;
+        out->rec.hist = reinterpret_cast<double*>(q); q += nhist;
+        out->rec.alog = reinterpret_cast<int32_t*>(q); q += nlog;
+        out->rec.ran = reinterpret_cast<int32_t*>(q);
+        out->flags_off = (size_t)(q - base);
+        out->flags_bytes = nflag;
+        q += nflag;
+        out->rec.n_obs = n_obs;
+        out->rec.T = (int32_t)T;
+        out->mean = sm.mean ? reinterpret_cast<double*>(q) : nullptr; q += sm.mean ? nrow : 0;
+        out->var = sm.var ? reinterpret_cast<double*>(q) : nullptr;
+    }
+    return nhist + nlog + nflag + (sm.mean ? nrow : 0) + (sm.var ? nrow : 0);
+}
+// the device times of a smoothed call's three parts: events on the stream, read after its end
+struct SsmSmoothClock {
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool on = false;
+    ~SsmSmoothClock() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    hipError_t start() {
+        for (hipEvent_t& e : ev) {
+            const hipError_t r = hipEventCreate(&e);
+            if (r != hipSuccess) return r;
+        }
+        on = true;
+        return hipSuccess;
+    }
+    hipError_t mark(int k, hipStream_t s) { return on ? hipEventRecord(ev[k], s) : hipSuccess; }
+    void read(wsmc_ctx* c, size_t bytes) {   // after the stream's end
+        for (int k = 0; k < 3; ++k) {
+            float ms = 0.0f;
+            c->ssm_smooth_us[k] = on && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess ? (int64_t)(ms * 1000.0f) : 0;
+        }
+        c->ssm_smooth_bytes = (int64_t)bytes;
+    }
+};
+static int ssm_smooth_alloc(SsmSlab* slab, size_t bytes, const char* who) {
+    const hipError_t e = hipMalloc(&slab->p, bytes);
+    if (e == hipSuccess) return WSMC_OK;
+    slab->p = nullptr;
+    (void)hipGetLastError();
+    if (e == hipErrorOutOfMemory)
+        return fail(WSMC_ENOMEM, std::string(who) + ": the device refused " + std::to_string(bytes) + " bytes for the history and the ancestor log");
+    return fail(WSMC_EHIP, std::string(who) + ": hipMalloc: " + hipGetErrorString(e));
+}
+
+// wsmc_ssm_run, wsmc_ssm_run_traced and wsmc_ssm_run_smoothed: tr's and sm's members are null where
+// nothing is wanted
 static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int32_t T, double ess_min, int32_t scheme,
-                   double* log_evidence_out, const wsmc_ssm_trace& tr) {
+                   double* log_evidence_out, const wsmc_ssm_trace& tr, const wsmc_ssm_smooth& sm) {
     double* const ess_trace_out = tr.ess;
     if (!c) return fail(WSMC_EARG, "null context");
     if (int rc = wsmc_ssm_spec_check(sp)) return rc;
@@ -5641,12 +5720,41 @@ static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int
     // SAMPLE never runs), and the programs within the kernel's arguments
     bool persistent = !c->multi && !is_sharded(c) && c->N <= ssm_cap(S) && scheme != WSMC_RESAMPLE_MULTINOMIAL &&
                       !c->weights_changed && nprog <= kSsmProgMax;
+    std::string foreign;
     if (persistent)
         for (const auto& col : c->cols) {
             bool in = false;
             for (int k = 0; k < S; ++k) in |= col.name == sp->col_names[k];
             persistent &= in;
+            if (!in && foreign.empty()) foreign = col.name;
         }
+    // a smoothed run has the persistent route only (the store could not drop the T n_cols columns
+    // the statements would leave): refused here, before anything of the context changes
+    const bool smooth = sm.paths || sm.mean || sm.var;
+    const int n_obs = ssm_count_observes(sp);
+    SsmSlab sm_slab;
+    SsmSmoothClock sm_clock;
+    size_t sm_bytes = 0;
+    SsmSmoothBufs sb;
+    std::memset(&sb, 0, sizeof(sb));
+    if (smooth) {
+        const std::string who = "ssm smoothed run: ";
+        if (c->multi || is_sharded(c)) return fail(WSMC_EARG, who + "a sharded or multi-device context (one unsharded device runs it)");
+        if (c->N > ssm_cap(S))
+            return fail(WSMC_EARG, who + "n = " + std::to_string(c->N) + " above the cap of " + std::to_string(ssm_cap(S)) +
+                                       " particles for " + std::to_string(S) + " columns");
+        if (scheme == WSMC_RESAMPLE_MULTINOMIAL)
+            return fail(WSMC_EARG, who + "multinomial resampling (the persistent workgroup has stratified and systematic)");
+        if (c->weights_changed) return fail(WSMC_EARG, who + "weights_changed is set (a Resample after a SAMPLE could run)");
+        if (nprog > kSsmProgMax)
+            return fail(WSMC_EARG, who + std::to_string(nprog) + " program instructions (more than " + std::to_string(kSsmProgMax) + ")");
+        if (!persistent) return fail(WSMC_EARG, who + "the context holds a column that is not the spec's (" + foreign + ")");
+        WSMC_HIP(hipSetDevice(c->device));
+        const size_t bytes = sm_bytes = ssm_smooth_carve(nullptr, sm, 1, T, c->N, S, n_obs, nullptr);
+        if (int rc = ssm_smooth_alloc(&sm_slab, bytes + 256, "ssm smoothed run")) return rc;
+        WSMC_HIP(sm_clock.start());
+        ssm_smooth_carve(sm_slab.p, sm, 1, T, c->N, S, n_obs, &sb);
+    }
     for (int k = 0; k < S; ++k)   // the missing ones, in order
         if (int rc = wsmc_col_create(c, sp->col_names[k], 1, &ids[k])) return rc;
     if (!persistent) {
@@ -5696,8 +5804,11 @@ static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int
     if (ndata > 0)
         WSMC_HIP(hipMemcpyAsync(c->lg_data, data, sizeof(double) * (size_t)ndata, hipMemcpyHostToDevice, c->stream));
     WSMC_HIP(hipMemsetAsync(c->lg_rec, 0, sizeof(LgRecord), c->stream));
-    SsmArgs ka;
-    std::memset(&ka, 0, sizeof(ka));
+    if (smooth) WSMC_HIP(hipMemsetAsync(sm_slab.p + sb.flags_off, 0, sb.flags_bytes, c->stream));
+    SsmRecArgs kra;   // (a smoothed run's launches: the same arguments and the log)
+    std::memset(&kra, 0, sizeof(kra));
+    SsmArgs& ka = kra.a;
+    kra.r = sb.rec;
     ka.tr_mean = n_mean ? c->ssm_rows : nullptr;
     ka.tr_var = n_var ? c->ssm_rows + n_mean : nullptr;
     ka.tr_logev = n_le ? c->ssm_rows + n_mean + n_var : nullptr;
@@ -5728,11 +5839,27 @@ static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int
     const int32_t K = c->ssm_segment > 0 ? c->ssm_segment
                                          : std::max(1, kSsmSegmentStmts / sp->n_step * 2 / std::max(2, (int)ka.P));
     int64_t nseg = 0;
+    WSMC_HIP(sm_clock.mark(0, c->stream));
     for (int32_t t0 = 0; t0 < T; t0 += K, ++nseg) {
         ka.t0 = t0;
         ka.nsteps = std::min<int32_t>(K, T - t0);
         ka.first = t0 == 0;
-        WSMC_HIP(launch_ssm_segment(c->stream, ka, feat, threads));
+        if (smooth)
+            WSMC_HIP(launch_ssm_segment_rec(c->stream, kra, feat, threads));
+        else
+            WSMC_HIP(launch_ssm_segment(c->stream, ka, feat, threads));
+    }
+    if (smooth) {   // the trace-back, then every row at once: on the stream, behind the last segment
+        WSMC_HIP(sm_clock.mark(1, c->stream));
+        WSMC_HIP(launch_ssm_traceback(c->stream, sb.rec, (int)c->N, 1));
+        WSMC_HIP(sm_clock.mark(2, c->stream));
+        WSMC_HIP(launch_ssm_smooth_rows(c->stream, sb.rec, c->w, sb.mean, sb.var, sm.paths != nullptr, (int)c->N, S, 1, threads));
+        WSMC_HIP(sm_clock.mark(3, c->stream));
+        if (sm.paths)
+            WSMC_HIP(hipMemcpyAsync(sm.paths, sb.rec.hist, sizeof(double) * (size_t)T * S * (size_t)c->N, hipMemcpyDeviceToHost,
+                                    c->stream));
+        if (sm.mean) WSMC_HIP(hipMemcpyAsync(sm.mean, sb.mean, sizeof(double) * (size_t)T * S, hipMemcpyDeviceToHost, c->stream));
+        if (sm.var) WSMC_HIP(hipMemcpyAsync(sm.var, sb.var, sizeof(double) * (size_t)T * S, hipMemcpyDeviceToHost, c->stream));
     }
     LgRecord hrec;
     WSMC_HIP(hipMemcpyAsync(&hrec, c->lg_rec, sizeof(LgRecord), hipMemcpyDeviceToHost, c->stream));
@@ -5773,6 +5900,7 @@ static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int
     c->weights_changed = 0;
     const auto t_booked = clk::now();
     WSMC_HIP(ctx_sync(c, c->stream));
+    if (smooth) sm_clock.read(c, sm_bytes);
     c->resampled = hrec.last_dec;
     c->last_ess = hrec.last_ess;
     c->n_resamples += hrec.nres;
@@ -5790,13 +5918,22 @@ static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int
 int wsmc_ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int32_t T, double ess_min, int32_t scheme,
                  double* log_evidence_out, double* ess_trace_out) {
     const wsmc_ssm_trace tr = {ess_trace_out, nullptr, nullptr, nullptr};
-    return ssm_run(c, sp, data, T, ess_min, scheme, log_evidence_out, tr);
+    const wsmc_ssm_smooth no_smooth = {nullptr, nullptr, nullptr};
+    return ssm_run(c, sp, data, T, ess_min, scheme, log_evidence_out, tr, no_smooth);
 }
 
 int wsmc_ssm_run_traced(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int32_t T, double ess_min, int32_t scheme,
                         double* log_evidence_out, const wsmc_ssm_trace* trace) {
     const wsmc_ssm_trace none = {nullptr, nullptr, nullptr, nullptr};
-    return ssm_run(c, sp, data, T, ess_min, scheme, log_evidence_out, trace ? *trace : none);
+    const wsmc_ssm_smooth no_smooth = {nullptr, nullptr, nullptr};
+    return ssm_run(c, sp, data, T, ess_min, scheme, log_evidence_out, trace ? *trace : none, no_smooth);
+}
+
+int wsmc_ssm_run_smoothed(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int32_t T, double ess_min, int32_t scheme,
+                          double* log_evidence_out, const wsmc_ssm_trace* trace, const wsmc_ssm_smooth* smooth) {
+    const wsmc_ssm_trace none = {nullptr, nullptr, nullptr, nullptr};
+    const wsmc_ssm_smooth no_smooth = {nullptr, nullptr, nullptr};
+    return ssm_run(c, sp, data, T, ess_min, scheme, log_evidence_out, trace ? *trace : none, smooth ? *smooth : no_smooth);
 }
 
 int wsmc_debug_ssm(wsmc_ctx* c, int32_t segment_steps, int64_t* stats_out) {
@@ -5888,7 +6025,7 @@ int wsmc_ssm_batch_out_sizeof(int64_t* bytes) {
 // wsmc_ssm_run_batch and wsmc_ssm_run_batch_traced: tr's members are null where nothing is wanted
 static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_specs, const double* data, int32_t n_tables,
                          int32_t T, int32_t n, int32_t B, const uint64_t* seeds, double ess_min, int32_t scheme,
-                         wsmc_ssm_batch_out* out, const wsmc_ssm_trace& tr) {
+                         wsmc_ssm_batch_out* out, const wsmc_ssm_trace& tr, const wsmc_ssm_smooth& sm) {
     // every refusal before any device call; the context's state is never read past its layout
     if (!c) return fail(WSMC_EARG, "null context");
     if (c->multi || is_sharded(c)) return fail(WSMC_EARG, "ssm batch: a sharded or multi-device context (one unsharded device runs a batch)");
@@ -5954,11 +6091,18 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
                  nmean = tr.mean ? up(sizeof(double) * (size_t)B * T * S) : 0, nvar = tr.var ? up(sizeof(double) * (size_t)B * T * S) : 0,
                  nle = tr.log_evidence ? up(sizeof(double) * (size_t)B * T) : 0;
     const size_t nstate = nx + nw + nanc + nrec;
-    struct Slab {
-        char* p = nullptr;
-        ~Slab() { if (p) (void)hipFree(p); }
-    } slab;
-    WSMC_HIP(hipMalloc(&slab.p, nstate + nfilt + ndata + ntrace + nmean + nvar + nle + 256));
+    const bool smooth = sm.paths || sm.mean || sm.var;
+    const int n_obs = ssm_count_observes(sp);
+    const size_t nsmooth = smooth ? ssm_smooth_carve(nullptr, sm, B, T, n, S, n_obs, nullptr) : 0;
+    SsmSlab slab;
+    SsmSmoothClock sm_clock;
+    if (smooth) {
+        if (int rc = ssm_smooth_alloc(&slab, nstate + nfilt + ndata + ntrace + nmean + nvar + nle + nsmooth + 256, "ssm smoothed batch"))
+            return rc;
+        WSMC_HIP(sm_clock.start());
+    } else {
+        WSMC_HIP(hipMalloc(&slab.p, nstate + nfilt + ndata + ntrace + nmean + nvar + nle + 256));
+    }
     char* q = slab.p;
     double* d_x = reinterpret_cast<double*>(q); q += nx;
     double* d_w = reinterpret_cast<double*>(q); q += nw;
@@ -5969,21 +6113,30 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
     double* d_trace = ntrace ? reinterpret_cast<double*>(q) : nullptr; q += ntrace;
     double* d_mean = nmean ? reinterpret_cast<double*>(q) : nullptr; q += nmean;
     double* d_var = nvar ? reinterpret_cast<double*>(q) : nullptr; q += nvar;
-    double* d_le = nle ? reinterpret_cast<double*>(q) : nullptr;
+    double* d_le = nle ? reinterpret_cast<double*>(q) : nullptr; q += nle;
+    SsmSmoothBufs sb;
+    std::memset(&sb, 0, sizeof(sb));
+    if (smooth) {
+        ssm_smooth_carve(q, sm, B, T, n, S, n_obs, &sb);
+        sb.flags_off += (size_t)(q - slab.p);
+    }
     for (int32_t b = 0; b < B; ++b)
         filt[(size_t)b].data = dd > 0 ? d_data + (size_t)(n_tables == 1 ? 0 : b) * T * dd : nullptr;
     hipStream_t st = c->stream;
     // (from here an error leaves through the stream's end, so nothing is freed under a kernel)
     auto run = [&]() -> hipError_t {
         hipError_t e = hipMemsetAsync(slab.p, 0, nstate, st);
+        if (e == hipSuccess && smooth) e = hipMemsetAsync(slab.p + sb.flags_off, 0, sb.flags_bytes, st);
         if (e == hipSuccess) e = hipMemcpyAsync(d_filt, filt.data(), sizeof(SsmBatchFilter) * (size_t)B, hipMemcpyHostToDevice, st);
         if (e == hipSuccess && dd > 0)
             e = hipMemcpyAsync(d_data, data, sizeof(double) * (size_t)n_tables * T * dd, hipMemcpyHostToDevice, st);
         return e;
     };
     hipError_t e = run();
-    SsmBatchArgs ka;
-    std::memset(&ka, 0, sizeof(ka));
+    SsmBatchRecArgs kra;   // (a smoothed batch's launches: the same arguments and the log)
+    std::memset(&kra, 0, sizeof(kra));
+    SsmBatchArgs& ka = kra.a;
+    kra.r = sb.rec;
     ka.x = d_x;
     ka.w = d_w;
     ka.anc = d_anc;
@@ -6010,7 +6163,7 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
     // steps a launch: the single run's, divided by the rounds of resident workgroups the batch
     // takes, so a launch stays near the single run's 25 ms whatever B is
     int per_cu = 0, cus = 0;
-    if (e == hipSuccess) e = ssm_batch_occupancy(c->device, feat, d_mean || d_var || d_le, threads, ssm_lds_bytes(n, S), &per_cu, &cus);
+    if (e == hipSuccess) e = ssm_batch_occupancy(c->device, feat, smooth ? 2 : (d_mean || d_var || d_le) ? 1 : 0, threads, ssm_lds_bytes(n, S), &per_cu, &cus);
     if (e == hipSuccess && (per_cu < 1 || cus < 1)) e = hipErrorInvalidValue;
     int64_t nseg = 0;
     if (e == hipSuccess) {
@@ -6018,14 +6171,20 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
         const int64_t rounds = ((int64_t)B + resident - 1) / resident;
         const int32_t K1 = std::max(1, kSsmSegmentStmts / sp->n_step * 2 / std::max(2, (int)ka.P));
         const int32_t K = c->ssm_batch_segment > 0 ? c->ssm_batch_segment : (int32_t)std::max<int64_t>(1, K1 / rounds);
+        e = sm_clock.mark(0, st);
         for (int32_t t0 = 0; t0 < T && e == hipSuccess; t0 += K, ++nseg) {
             ka.t0 = t0;
             ka.nsteps = std::min<int32_t>(K, T - t0);
             ka.first = t0 == 0;
             ka.last = t0 + ka.nsteps == T;
-            e = launch_ssm_batch_segment(st, ka, feat, threads);
+            e = smooth ? launch_ssm_batch_segment_rec(st, kra, feat, threads) : launch_ssm_batch_segment(st, ka, feat, threads);
         }
     }
+    if (e == hipSuccess) e = sm_clock.mark(1, st);
+    if (e == hipSuccess && smooth) e = launch_ssm_traceback(st, sb.rec, n, B);
+    if (e == hipSuccess) e = sm_clock.mark(2, st);
+    if (e == hipSuccess && smooth) e = launch_ssm_smooth_rows(st, sb.rec, d_w, sb.mean, sb.var, sm.paths != nullptr, n, S, B, threads);
+    if (e == hipSuccess) e = sm_clock.mark(3, st);
     std::vector<SsmBatchRec> hrec((size_t)B);
     auto down = [&](void* host, const void* dev, size_t bytes) {
         if (e == hipSuccess && host) e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st);
@@ -6036,6 +6195,11 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
     down(tr.mean, d_mean, sizeof(double) * (size_t)B * T * S);
     down(tr.var, d_var, sizeof(double) * (size_t)B * T * S);
     down(tr.log_evidence, d_le, sizeof(double) * (size_t)B * T);
+    if (smooth) {
+        down(sm.paths, sb.rec.hist, sizeof(double) * (size_t)B * T * S * n);
+        down(sm.mean, sb.mean, sizeof(double) * (size_t)B * T * S);
+        down(sm.var, sb.var, sizeof(double) * (size_t)B * T * S);
+    }
     down(out->cols, d_x, sizeof(double) * (size_t)B * S * n);
     down(out->log_weights, d_w, sizeof(double) * (size_t)B * n);
     down(out->last_ancestors, d_anc, sizeof(int32_t) * (size_t)B * n);
@@ -6057,6 +6221,7 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
         if (out->n_resamples) out->n_resamples[b] = r.nres;
         if (out->last_resampled) out->last_resampled[b] = r.last_dec;
     }
+    if (smooth) sm_clock.read(c, nsmooth);
     c->ssm_batch_per_cu = per_cu;
     c->ssm_batch_cus = cus;
     c->ssm_batch_segments = nseg;
@@ -6068,14 +6233,34 @@ int wsmc_ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_specs,
                        int32_t T, int32_t n, int32_t B, const uint64_t* seeds, double ess_min, int32_t scheme,
                        wsmc_ssm_batch_out* out) {
     const wsmc_ssm_trace none = {nullptr, nullptr, nullptr, nullptr};
-    return ssm_run_batch(c, specs, n_specs, data, n_tables, T, n, B, seeds, ess_min, scheme, out, none);
+    const wsmc_ssm_smooth no_smooth = {nullptr, nullptr, nullptr};
+    return ssm_run_batch(c, specs, n_specs, data, n_tables, T, n, B, seeds, ess_min, scheme, out, none, no_smooth);
 }
 
 int wsmc_ssm_run_batch_traced(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_specs, const double* data, int32_t n_tables,
                               int32_t T, int32_t n, int32_t B, const uint64_t* seeds, double ess_min, int32_t scheme,
                               wsmc_ssm_batch_out* out, const wsmc_ssm_trace* trace) {
     const wsmc_ssm_trace none = {nullptr, nullptr, nullptr, nullptr};
-    return ssm_run_batch(c, specs, n_specs, data, n_tables, T, n, B, seeds, ess_min, scheme, out, trace ? *trace : none);
+    const wsmc_ssm_smooth no_smooth = {nullptr, nullptr, nullptr};
+    return ssm_run_batch(c, specs, n_specs, data, n_tables, T, n, B, seeds, ess_min, scheme, out, trace ? *trace : none, no_smooth);
+}
+
+int wsmc_ssm_run_batch_smoothed(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_specs, const double* data, int32_t n_tables,
+                                int32_t T, int32_t n, int32_t B, const uint64_t* seeds, double ess_min, int32_t scheme,
+                                wsmc_ssm_batch_out* out, const wsmc_ssm_trace* trace, const wsmc_ssm_smooth* smooth) {
+    const wsmc_ssm_trace none = {nullptr, nullptr, nullptr, nullptr};
+    const wsmc_ssm_smooth no_smooth = {nullptr, nullptr, nullptr};
+    return ssm_run_batch(c, specs, n_specs, data, n_tables, T, n, B, seeds, ess_min, scheme, out, trace ? *trace : none,
+                         smooth ? *smooth : no_smooth);
+}
+
+int wsmc_debug_ssm_smooth(wsmc_ctx* c, int64_t* stats_out) {
+    if (!c) return fail(WSMC_EARG, "null context");
+    if (c->multi) return fail(WSMC_EARG, "ssm smoothed run: a multi-device context");
+    if (!stats_out) return fail(WSMC_EARG, "null stats_out");
+    for (int k = 0; k < 3; ++k) stats_out[k] = c->ssm_smooth_us[k];
+    stats_out[3] = c->ssm_smooth_bytes;
+    return WSMC_OK;
 }
 
 int wsmc_debug_ssm_batch(wsmc_ctx* c, int32_t segment_steps, int64_t* stats_out) {

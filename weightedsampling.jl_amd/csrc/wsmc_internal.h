@@ -390,6 +390,9 @@ struct wsmc_ctx {
     // default), then the last call's resident blocks per CU, CU count, segments and wall time
     int32_t ssm_batch_segment = 0;
     int64_t ssm_batch_per_cu = 0, ssm_batch_cus = 0, ssm_batch_segments = 0, ssm_batch_wall_us = 0;
+    // the last smoothed run or batch (wsmc_debug_ssm_smooth): device microseconds of the segments,
+    // the trace-back and the rows kernel, and the bytes of the log
+    int64_t ssm_smooth_us[3] = {0, 0, 0}, ssm_smooth_bytes = 0;
     bool timing = false;
     std::vector<hipEvent_t> events;
     wsmc_run_timing last_timing{};
@@ -969,11 +972,41 @@ struct SsmArgs {
     SsmIns ins[kSsmProgMax];
 };
 static_assert(sizeof(SsmArgs) + 32 <= 4096, "the spec rides in the kernel arguments");
+// A smoothed run (wsmc_ssm_run_smoothed, csrc/wsmc_ssm_smooth.hip): what the recording kernels log
+// to device memory. hist: the columns at every trace point; alog: one slot per (step, OBSERVE of
+// the step) for the ancestors of the Resample that follows the OBSERVE, written when it ran, with
+// the slot's flag in `ran` (zeroed before the run), so nothing is carried across launches. A
+// Resample after a SAMPLE never runs and has no slot. A batch's filter b has its own [T] rows.
+struct SsmRec {
+    double* hist;             // [B][T][S][N]
+    int32_t* alog;            // [B][T * n_obs][N]
+    int32_t* ran;             // [B][T * n_obs]
+    int32_t n_obs, T;         // OBSERVEs a step; the run's steps (a filter's stride)
+};
+// the recording kernel's arguments: the run's own, unchanged and first, so that the kernels of the
+// untraced and traced units keep their argument layout
+struct SsmRecArgs {
+    SsmArgs a;
+    SsmRec r;
+};
+static_assert(sizeof(SsmRecArgs) + 32 <= 4096, "the spec rides in the kernel arguments");
 size_t ssm_lds_bytes(int n, int S);
 // feat: WSMC_FEAT_EXT / WSMC_FEAT_GAM bits over the spec's dists (the kernel's instantiation)
 int ssm_threads(unsigned feat, int n);
 // (the traced instantiation when a tr_ pointer is set, else the one an untraced run has always had)
 hipError_t launch_ssm_segment(hipStream_t s, const SsmArgs& a, unsigned feat, int threads);
+// the recording instantiation (always a traced one: its tr_ pointers may all be null)
+hipError_t launch_ssm_segment_rec(hipStream_t s, const SsmRecArgs& a, unsigned feat, int threads);
+// After the run's last segment (csrc/wsmc_ssm_smooth.hip), for B filters of T steps:
+// launch_ssm_traceback follows every final particle back through the log, one workgroup a filter,
+// and leaves idx_t (final particle i's ancestor at trace point t) in place over slot
+// (t, n_obs - 1); launch_ssm_smooth_rows, one workgroup a (filter, step), gathers row t of hist
+// through idx_t in place and takes wsmc_weighted_moments of it under the final weights w [B][N]
+// (ss_trace_row's canonical sums). mean / var: [B][T][S], null: not wanted; paths: whether hist
+// is read afterwards (without it the gathered row is not written back).
+hipError_t launch_ssm_traceback(hipStream_t s, const SsmRec& r, int N, int B);
+hipError_t launch_ssm_smooth_rows(hipStream_t s, const SsmRec& r, const double* w, double* mean, double* var, bool paths,
+                                  int N, int S, int B, int threads);
 // B independent runs of that kernel's step body in one launch, one workgroup a filter
 // (csrc/wsmc_ssm_batch.hip, wsmc_ssm_run_batch). The statements' shape is one for the batch, their
 // numbers are not, so each filter reads its own image of the compact statements from device
@@ -1012,9 +1045,15 @@ struct SsmBatchArgs {
     int32_t T, B;
     double ess_min;
 };
-// blocks of the variant that are resident on one CU (by registers, waves and LDS), and the device's CUs
-hipError_t ssm_batch_occupancy(int device, unsigned feat, bool traced, int threads, size_t lds, int* per_cu, int* cus);
+struct SsmBatchRecArgs {      // the recording batch kernel's arguments (see SsmRecArgs)
+    SsmBatchArgs a;
+    SsmRec r;
+};
+// blocks of the variant that are resident on one CU (by registers, waves and LDS), and the device's CUs.
+// variant: 0 untraced, 1 traced, 2 recording
+hipError_t ssm_batch_occupancy(int device, unsigned feat, int variant, int threads, size_t lds, int* per_cu, int* cus);
 hipError_t launch_ssm_batch_segment(hipStream_t s, const SsmBatchArgs& a, unsigned feat, int threads);
+hipError_t launch_ssm_batch_segment_rec(hipStream_t s, const SsmBatchRecArgs& a, unsigned feat, int threads);
 // one handle over several devices (wsmc_multi.hip): the ABI entry points fan out
 int multi_destroy(wsmc_ctx* c);
 wsmc_ctx* multi_first(wsmc_ctx* c);

@@ -31,12 +31,25 @@ namespace wsmc {
 // unit of their own keeps the untraced kernels what the compiler made of them before there was a
 // trace: with six kernels in one unit instead of three the inliner's choices change and the
 // log-Gamma variant goes from 116 VGPRs to 128 and spills.
-#ifdef WSMC_SSM_TRACED
+// A third time through csrc/wsmc_ssm_smooth.hip (WSMC_SSM_SMOOTH) for the recording ones of a
+// smoothed run: traced instantiations that also log the trace point's columns and each Resample's
+// ancestors (SsmRec). They are a kernel of another name with arguments of their own, so the other
+// two units' kernels are, to the instruction, what they were before there was a log.
+#if defined(WSMC_SSM_SMOOTH)
+constexpr bool kSsTraced = true;
+#define WSMC_SSM_VARIANTS ssm_launch_rec
+#define WSMC_SSM_KERNEL k_ssm_segment_rec
+typedef SsmRecArgs SsKernArgs;
+#elif defined(WSMC_SSM_TRACED)
 constexpr bool kSsTraced = true;
 #define WSMC_SSM_VARIANTS ssm_launch_traced
+#define WSMC_SSM_KERNEL k_ssm_segment
+typedef SsmArgs SsKernArgs;
 #else
 constexpr bool kSsTraced = false;
 #define WSMC_SSM_VARIANTS ssm_launch_untraced
+#define WSMC_SSM_KERNEL k_ssm_segment
+typedef SsmArgs SsKernArgs;
 
 // the kernel's dynamic LDS for n particles in S columns (beside the 4 KiB of static log / exp tables)
 size_t ssm_lds_bytes(int n, int S) {
@@ -47,8 +60,12 @@ size_t ssm_lds_bytes(int n, int S) {
 // TR: the traced run (wsmc_ssm_run_traced), which also leaves row t of the moments and the evidence
 // at the ESS trace's point
 template <unsigned FEAT, int THREADS, bool TR>
-__global__ __launch_bounds__(THREADS) void k_ssm_segment(SsmArgs) {
+__global__ __launch_bounds__(THREADS) void WSMC_SSM_KERNEL(SsKernArgs) {
     const SsmArgs& a = *(const SsmArgs*)(const char*)__builtin_amdgcn_kernarg_segment_ptr();
+#ifdef WSMC_SSM_SMOOTH
+    static_assert(offsetof(SsmRecArgs, a) == 0, "the run's arguments come first");
+    const SsmRec& rc = *(const SsmRec*)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(SsmRecArgs, r));
+#endif
     extern __shared__ __attribute__((aligned(16))) char ss_smem[];
     const int tid = (int)threadIdx.x, nthr = (int)blockDim.x;
     const int N = a.N, P = a.P, S = a.S;
@@ -102,6 +119,9 @@ __global__ __launch_bounds__(THREADS) void k_ssm_segment(SsmArgs) {
             dv = dnext;
             if (s + 1 < a.nsteps) dnext = ss_row(data, dd, t + 1);   // in flight during this step
         }
+#ifdef WSMC_SSM_SMOOTH
+        int slot = t * rc.n_obs;   // the log's slot of the step's next OBSERVE
+#endif
         for (int q = 0; q < nst; ++q) {
             const SsmStmt& st = list[q];
             ss_statement<FEAT>(st, a.ins, L, dv, a.seed, op);
@@ -109,9 +129,18 @@ __global__ __launch_bounds__(THREADS) void k_ssm_segment(SsmArgs) {
                 op += 2;   // the draws, then a Resample that does not run (the weights have not changed)
             } else if (st.kind == WSMC_SSM_OBSERVE) {
                 const bool row = TR && !init && q == a.last_obs;
+#ifdef WSMC_SSM_SMOOTH
+                if (row) ss_record_cols(L, rc.hist + (size_t)t * S * N);
+#endif
                 if (row && (a.tr_mean || a.tr_var))
                     ss_trace_row(L, a.tr_mean ? a.tr_mean + (size_t)t * S : nullptr, a.tr_var ? a.tr_var + (size_t)t * S : nullptr);
                 const SsDecision d = ss_resample<TR>(L, K, a.ess_min, a.scheme, a.seed, op);
+#ifdef WSMC_SSM_SMOOTH
+                if (!init) {
+                    if (d.resampled) ss_record_anc(L, rc.alog + (size_t)slot * N, rc.ran + slot);
+                    slot += 1;
+                }
+#endif
                 if (row && a.tr_logev && tid == 0) a.tr_logev[t] = d.logev;
                 op += 1;
                 nres += d.resampled;
@@ -139,23 +168,23 @@ __global__ __launch_bounds__(THREADS) void k_ssm_segment(SsmArgs) {
 }
 
 template <unsigned FEAT, int THREADS>
-static hipError_t ssm_launch(hipStream_t s, const SsmArgs& a, int threads, size_t lds) {
+static hipError_t ssm_launch(hipStream_t s, const SsKernArgs& a, int threads, size_t lds) {
     if (lds > 65536 - 4096) {   // past 64 KiB a kernel must ask for its dynamic LDS (per device: set at each launch)
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ssm_segment<FEAT, THREADS, kSsTraced>),
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(WSMC_SSM_KERNEL<FEAT, THREADS, kSsTraced>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((k_ssm_segment<FEAT, THREADS, kSsTraced>), dim3(1), dim3(threads), lds, s, a);
+    hipLaunchKernelGGL((WSMC_SSM_KERNEL<FEAT, THREADS, kSsTraced>), dim3(1), dim3(threads), lds, s, a);
     return hipGetLastError();
 }
 // this unit's three feature variants (launch_ssm_segment has checked the arguments)
-hipError_t WSMC_SSM_VARIANTS(hipStream_t s, const SsmArgs& a, unsigned feat, int threads, size_t lds) {
+hipError_t WSMC_SSM_VARIANTS(hipStream_t s, const SsKernArgs& a, unsigned feat, int threads, size_t lds) {
     if (feat & WSMC_FEAT_GAM) return ssm_launch<kSsFeatGam, kSsGamThreads>(s, a, threads, lds);
     if (feat & WSMC_FEAT_EXT) return ssm_launch<kSsFeatExt, kSsMaxThreads>(s, a, threads, lds);
     return ssm_launch<0u, kSsMaxThreads>(s, a, threads, lds);
 }
 
-#ifndef WSMC_SSM_TRACED
+#if !defined(WSMC_SSM_TRACED) && !defined(WSMC_SSM_SMOOTH)
 int ssm_threads(unsigned feat, int n) {
     const int cap = (feat & WSMC_FEAT_GAM) ? kSsGamThreads : kSsMaxThreads;
     // two particles a thread where the workgroup allows (wsmc_lgssm1d_run's measured choice)
@@ -164,17 +193,29 @@ int ssm_threads(unsigned feat, int n) {
 
 hipError_t ssm_launch_traced(hipStream_t s, const SsmArgs& a, unsigned feat, int threads, size_t lds);   // csrc/wsmc_ssm_traced.hip
 
-hipError_t launch_ssm_segment(hipStream_t s, const SsmArgs& a, unsigned feat, int threads) {
+hipError_t ssm_launch_rec(hipStream_t s, const SsmRecArgs& a, unsigned feat, int threads, size_t lds);   // csrc/wsmc_ssm_smooth.hip
+
+static bool ssm_segment_ok(const SsmArgs& a, unsigned feat, int threads) {
     const int tmax = (feat & WSMC_FEAT_GAM) ? kSsGamThreads : kSsMaxThreads;
-    if (a.S < 1 || a.S > WSMC_SSM_MAX_COLS || a.N < 1 || a.N > ssm_cap(a.S) || threads < 64 || threads > tmax ||
+    return !(a.S < 1 || a.S > WSMC_SSM_MAX_COLS || a.N < 1 || a.N > ssm_cap(a.S) || threads < 64 || threads > tmax ||
         (threads & 63) || (int64_t)a.P * threads < a.N || a.nsteps < 0 || a.t0 < 0 || a.data_dim < 0 ||
         a.data_dim > WSMC_SSM_MAX_DATA || a.n_init < 0 || a.n_init > WSMC_SSM_MAX_INIT || a.n_step < 1 ||
-        a.n_step > WSMC_SSM_MAX_STMTS)
-        return hipErrorInvalidValue;
+        a.n_step > WSMC_SSM_MAX_STMTS) &&
+           ssm_lds_bytes(a.N, a.S) + 4096 <= 160 * 1024;   // with the static tables: the workgroup's LDS
+}
+
+hipError_t launch_ssm_segment(hipStream_t s, const SsmArgs& a, unsigned feat, int threads) {
+    if (!ssm_segment_ok(a, feat, threads)) return hipErrorInvalidValue;
     const size_t lds = ssm_lds_bytes(a.N, a.S);
-    if (lds + 4096 > 160 * 1024) return hipErrorInvalidValue;   // with the static tables: the workgroup's LDS
     if (a.tr_mean || a.tr_var || a.tr_logev) return ssm_launch_traced(s, a, feat, threads, lds);
     return ssm_launch_untraced(s, a, feat, threads, lds);
+}
+
+hipError_t launch_ssm_segment_rec(hipStream_t s, const SsmRecArgs& a, unsigned feat, int threads) {
+    if (!ssm_segment_ok(a.a, feat, threads) || !a.r.hist || !a.r.alog || !a.r.ran || a.r.n_obs < 1 ||
+        a.a.t0 + a.a.nsteps > a.r.T)
+        return hipErrorInvalidValue;
+    return ssm_launch_rec(s, a, feat, threads, ssm_lds_bytes(a.a.N, a.a.S));
 }
 #endif
 

@@ -23,14 +23,26 @@ namespace wsmc {
 
 // compiled twice, as csrc/wsmc_ssm.hip is: as it stands for the untraced instantiations, through
 // csrc/wsmc_ssm_batch_traced.hip (WSMC_SSM_TRACED) for the traced ones
-#ifdef WSMC_SSM_TRACED
+// and through csrc/wsmc_ssm_batch_smooth.hip (WSMC_SSM_SMOOTH) for the recording ones of a smoothed
+// batch: a kernel of another name with arguments of its own, as in csrc/wsmc_ssm.hip
+#if defined(WSMC_SSM_SMOOTH)
+constexpr bool kSsbTraced = true;
+#define WSMC_SSB_OCCUPANCY ssb_occupancy_rec
+#define WSMC_SSB_VARIANTS ssb_launch_rec
+#define WSMC_SSB_KERNEL k_ssm_batch_segment_rec
+typedef SsmBatchRecArgs SsbKernArgs;
+#elif defined(WSMC_SSM_TRACED)
 constexpr bool kSsbTraced = true;
 #define WSMC_SSB_OCCUPANCY ssb_occupancy_traced
 #define WSMC_SSB_VARIANTS ssb_launch_traced
+#define WSMC_SSB_KERNEL k_ssm_batch_segment
+typedef SsmBatchArgs SsbKernArgs;
 #else
 constexpr bool kSsbTraced = false;
 #define WSMC_SSB_OCCUPANCY ssb_occupancy_untraced
 #define WSMC_SSB_VARIANTS ssb_launch_untraced
+#define WSMC_SSB_KERNEL k_ssm_batch_segment
+typedef SsmBatchArgs SsbKernArgs;
 #endif
 
 namespace {
@@ -39,10 +51,21 @@ typedef const SsmBatchFilter __attribute__((address_space(4))) * SsFilterPtr;
 
 // TR: the traced batch (wsmc_ssm_run_batch_traced), k_ssm_segment's flag
 template <unsigned FEAT, int THREADS, bool TR>
-__global__ __launch_bounds__(THREADS) void k_ssm_batch_segment(const SsmBatchArgs a) {
+#ifdef WSMC_SSM_SMOOTH
+__global__ __launch_bounds__(THREADS) void WSMC_SSB_KERNEL(const SsmBatchRecArgs ka) {
+    const SsmBatchArgs& a = ka.a;
+#else
+__global__ __launch_bounds__(THREADS) void WSMC_SSB_KERNEL(const SsmBatchArgs a) {
+#endif
     extern __shared__ __attribute__((aligned(16))) char ssb_smem[];
     const int tid = (int)threadIdx.x, nthr = (int)blockDim.x;
     const size_t b = blockIdx.x;
+#ifdef WSMC_SSM_SMOOTH
+    // filter b's rows of the history and of the log
+    double* hist = ka.r.hist + b * (size_t)ka.r.T * (size_t)a.S * (size_t)a.N;
+    int32_t* alog = ka.r.alog + b * (size_t)ka.r.T * (size_t)ka.r.n_obs * (size_t)a.N;
+    int32_t* ranf = ka.r.ran + b * (size_t)ka.r.T * (size_t)ka.r.n_obs;
+#endif
     const SsmBatchFilter& f = *(const SsmBatchFilter*)((SsFilterPtr)a.filt + b);
     const int N = a.N, P = a.P, S = a.S;
     SsState L;
@@ -100,6 +123,9 @@ __global__ __launch_bounds__(THREADS) void k_ssm_batch_segment(const SsmBatchArg
             dv = dnext;
             if (s + 1 < a.nsteps) dnext = ss_row(data, dd, t + 1);   // in flight during this step
         }
+#ifdef WSMC_SSM_SMOOTH
+        int slot = t * ka.r.n_obs;   // the log's slot of the step's next OBSERVE
+#endif
         for (int q = 0; q < nst; ++q) {
             const SsmStmt& st = list[q];
             ss_statement<FEAT>(st, f.ins, L, dv, seed, op);
@@ -108,9 +134,18 @@ __global__ __launch_bounds__(THREADS) void k_ssm_batch_segment(const SsmBatchArg
             } else if (st.kind == WSMC_SSM_OBSERVE) {
                 const bool row = TR && !init && q == a.last_obs;
                 const size_t r = b * (size_t)a.T + (size_t)t;
+#ifdef WSMC_SSM_SMOOTH
+                if (row) ss_record_cols(L, hist + (size_t)t * S * N);
+#endif
                 if (row && (a.tr_mean || a.tr_var))
                     ss_trace_row(L, a.tr_mean ? a.tr_mean + r * S : nullptr, a.tr_var ? a.tr_var + r * S : nullptr);
                 const SsDecision d = ss_resample<TR>(L, K, a.ess_min, a.scheme, seed, op);
+#ifdef WSMC_SSM_SMOOTH
+                if (!init) {
+                    if (d.resampled) ss_record_anc(L, alog + (size_t)slot * N, ranf + slot);
+                    slot += 1;
+                }
+#endif
                 if (row && a.tr_logev && tid == 0) a.tr_logev[r] = d.logev;
                 op += 1;
                 nres += d.resampled;
@@ -187,7 +222,7 @@ namespace {
 
 template <unsigned FEAT, int THREADS>
 hipError_t ssb_occupancy(int threads, size_t lds, int* per_cu) {
-    const void* k = reinterpret_cast<const void*>(k_ssm_batch_segment<FEAT, THREADS, kSsbTraced>);
+    const void* k = reinterpret_cast<const void*>(WSMC_SSB_KERNEL<FEAT, THREADS, kSsbTraced>);
     if (lds > 65536 - 4096) {   // the occupancy query refuses dynamic LDS the kernel has not asked for
         const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
@@ -196,13 +231,13 @@ hipError_t ssb_occupancy(int threads, size_t lds, int* per_cu) {
 }
 
 template <unsigned FEAT, int THREADS>
-hipError_t ssb_launch(hipStream_t s, const SsmBatchArgs& a, int threads, size_t lds) {
+hipError_t ssb_launch(hipStream_t s, const SsbKernArgs& a, int threads, size_t lds, int B) {
     if (lds > 65536 - 4096) {   // past 64 KiB a kernel must ask for its dynamic LDS (per device: set at each launch)
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ssm_batch_segment<FEAT, THREADS, kSsbTraced>),
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(WSMC_SSB_KERNEL<FEAT, THREADS, kSsbTraced>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((k_ssm_batch_segment<FEAT, THREADS, kSsbTraced>), dim3((unsigned)a.B), dim3(threads), lds, s, a);
+    hipLaunchKernelGGL((WSMC_SSB_KERNEL<FEAT, THREADS, kSsbTraced>), dim3((unsigned)B), dim3(threads), lds, s, a);
     return hipGetLastError();
 }
 
@@ -214,33 +249,45 @@ hipError_t WSMC_SSB_OCCUPANCY(unsigned feat, int threads, size_t lds, int* per_c
     if (feat & WSMC_FEAT_EXT) return ssb_occupancy<kSsFeatExt, kSsMaxThreads>(threads, lds, per_cu);
     return ssb_occupancy<0u, kSsMaxThreads>(threads, lds, per_cu);
 }
-hipError_t WSMC_SSB_VARIANTS(hipStream_t s, const SsmBatchArgs& a, unsigned feat, int threads, size_t lds) {
-    if (feat & WSMC_FEAT_GAM) return ssb_launch<kSsFeatGam, kSsGamThreads>(s, a, threads, lds);
-    if (feat & WSMC_FEAT_EXT) return ssb_launch<kSsFeatExt, kSsMaxThreads>(s, a, threads, lds);
-    return ssb_launch<0u, kSsMaxThreads>(s, a, threads, lds);
+hipError_t WSMC_SSB_VARIANTS(hipStream_t s, const SsbKernArgs& a, unsigned feat, int threads, size_t lds, int B) {
+    if (feat & WSMC_FEAT_GAM) return ssb_launch<kSsFeatGam, kSsGamThreads>(s, a, threads, lds, B);
+    if (feat & WSMC_FEAT_EXT) return ssb_launch<kSsFeatExt, kSsMaxThreads>(s, a, threads, lds, B);
+    return ssb_launch<0u, kSsMaxThreads>(s, a, threads, lds, B);
 }
 
-#ifndef WSMC_SSM_TRACED
+#if !defined(WSMC_SSM_TRACED) && !defined(WSMC_SSM_SMOOTH)
 hipError_t ssb_occupancy_traced(unsigned feat, int threads, size_t lds, int* per_cu);   // csrc/wsmc_ssm_batch_traced.hip
-hipError_t ssb_launch_traced(hipStream_t s, const SsmBatchArgs& a, unsigned feat, int threads, size_t lds);
+hipError_t ssb_launch_traced(hipStream_t s, const SsmBatchArgs& a, unsigned feat, int threads, size_t lds, int B);
+hipError_t ssb_occupancy_rec(unsigned feat, int threads, size_t lds, int* per_cu);      // csrc/wsmc_ssm_batch_smooth.hip
+hipError_t ssb_launch_rec(hipStream_t s, const SsmBatchRecArgs& a, unsigned feat, int threads, size_t lds, int B);
 
-hipError_t ssm_batch_occupancy(int device, unsigned feat, bool traced, int threads, size_t lds, int* per_cu, int* cus) {
+hipError_t ssm_batch_occupancy(int device, unsigned feat, int variant, int threads, size_t lds, int* per_cu, int* cus) {
     const hipError_t e = hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, device);
     if (e != hipSuccess) return e;
-    return traced ? ssb_occupancy_traced(feat, threads, lds, per_cu) : ssb_occupancy_untraced(feat, threads, lds, per_cu);
+    if (variant == 2) return ssb_occupancy_rec(feat, threads, lds, per_cu);
+    return variant ? ssb_occupancy_traced(feat, threads, lds, per_cu) : ssb_occupancy_untraced(feat, threads, lds, per_cu);
+}
+
+static bool ssb_segment_ok(const SsmBatchArgs& a, unsigned feat, int threads) {
+    const int tmax = (feat & WSMC_FEAT_GAM) ? kSsGamThreads : kSsMaxThreads;
+    return !(a.B < 1 || a.S < 1 || a.S > WSMC_SSM_MAX_COLS || a.N < 1 || a.N > ssm_cap(a.S) || threads < 64 || threads > tmax ||
+        (threads & 63) || (int64_t)a.P * threads < a.N || a.nsteps < 0 || a.t0 < 0 || a.t0 + a.nsteps > a.T ||
+        a.data_dim < 0 || a.data_dim > WSMC_SSM_MAX_DATA || a.n_init < 0 || a.n_init > WSMC_SSM_MAX_INIT || a.n_step < 1 ||
+        a.n_step > WSMC_SSM_MAX_STMTS || !a.x || !a.w || !a.anc || !a.rec || !a.filt) &&
+           ssm_lds_bytes(a.N, a.S) + 4096 <= 160 * 1024;   // with the static tables: the workgroup's LDS
 }
 
 hipError_t launch_ssm_batch_segment(hipStream_t s, const SsmBatchArgs& a, unsigned feat, int threads) {
-    const int tmax = (feat & WSMC_FEAT_GAM) ? kSsGamThreads : kSsMaxThreads;
-    if (a.B < 1 || a.S < 1 || a.S > WSMC_SSM_MAX_COLS || a.N < 1 || a.N > ssm_cap(a.S) || threads < 64 || threads > tmax ||
-        (threads & 63) || (int64_t)a.P * threads < a.N || a.nsteps < 0 || a.t0 < 0 || a.t0 + a.nsteps > a.T ||
-        a.data_dim < 0 || a.data_dim > WSMC_SSM_MAX_DATA || a.n_init < 0 || a.n_init > WSMC_SSM_MAX_INIT || a.n_step < 1 ||
-        a.n_step > WSMC_SSM_MAX_STMTS || !a.x || !a.w || !a.anc || !a.rec || !a.filt)
-        return hipErrorInvalidValue;
+    if (!ssb_segment_ok(a, feat, threads)) return hipErrorInvalidValue;
     const size_t lds = ssm_lds_bytes(a.N, a.S);
-    if (lds + 4096 > 160 * 1024) return hipErrorInvalidValue;   // with the static tables: the workgroup's LDS
-    if (a.tr_mean || a.tr_var || a.tr_logev) return ssb_launch_traced(s, a, feat, threads, lds);
-    return ssb_launch_untraced(s, a, feat, threads, lds);
+    if (a.tr_mean || a.tr_var || a.tr_logev) return ssb_launch_traced(s, a, feat, threads, lds, a.B);
+    return ssb_launch_untraced(s, a, feat, threads, lds, a.B);
+}
+
+hipError_t launch_ssm_batch_segment_rec(hipStream_t s, const SsmBatchRecArgs& a, unsigned feat, int threads) {
+    if (!ssb_segment_ok(a.a, feat, threads) || !a.r.hist || !a.r.alog || !a.r.ran || a.r.n_obs < 1 || a.r.T != a.a.T)
+        return hipErrorInvalidValue;
+    return ssb_launch_rec(s, a, feat, threads, ssm_lds_bytes(a.a.N, a.a.S), a.a.B);
 }
 #endif
 

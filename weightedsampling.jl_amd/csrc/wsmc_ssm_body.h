@@ -459,6 +459,23 @@ __device__ inline void ss_trace_row(SsState& L, double* mean_out, double* var_ou
         for (int k = 0; k < S; ++k) var_out[k] = ss_canon_total(wv2 + k, WSMC_SSM_MAX_COLS, ntiles) / S0;
 }
 
+// ---- a smoothed run's recording (wsmc_ssm_run_smoothed; the recording units alone call these) ----
+// The trace point's columns to row t of the history, every thread its own particles: plain stores,
+// nothing waits on them. hist: the row's [S][N] doubles in global memory
+__device__ inline void ss_record_cols(const SsState& L, double* hist) {
+    for (int k = 0; k < L.S; ++k) {
+        const double* src = L.cb + ss_buf(L, k) * L.stride;
+        double* dst = hist + (size_t)k * L.N;
+        for (int i = L.i0; i < L.i1; ++i) dst[i] = src[i];
+    }
+}
+// After a Resample that ran: its ancestors (each written by its particle's owner in ss_resample)
+// to the slot's [N] row of the log, and the slot's flag
+__device__ inline void ss_record_anc(const SsState& L, int32_t* slot, int32_t* ran) {
+    for (int i = L.i0; i < L.i1; ++i) slot[i] = L.anc[i];
+    if (L.lane == 0 && L.wave == 0) *ran = 1;
+}
+
 // The instantiations by feature set (k_sample<...>'s): a spec without the log-Gamma families
 // never carries wsmc_lgamma and the rejection samplers, one without the extended scalar
 // families not their code either. Each variant has its own launch bound; all three fit the 128

@@ -974,4 +974,79 @@ function ssm_run_batch_traced(state::HipState, specs, data, n::Integer, seeds::A
             log_evidence_trace=le, cols=cols, log_weights=lw, last_ancestors=anc)
 end
 
+# wsmc_ssm_smooth (include/wsmc.h): host buffers of the smoothed output, C_NULL for the ones not wanted
+struct WsmcSsmSmooth
+    paths::Ptr{Float64}
+    mean::Ptr{Float64}
+    var::Ptr{Float64}
+end
+
+"""
+    ssm_run_smoothed!(state, spec, data; scheme, paths=true) -> (log_evidence, smooth)
+
+`ssm_run!` with the final particles' trajectories and the smoothed moments (`wsmc_ssm_run_smoothed`):
+`smooth.paths` (n x n_cols x T: column k at step t's trace point of final particle i's ancestor, the
+reference's `x{t+1}` history columns; `nothing` without `paths`), `smooth.mean` and `smooth.var`
+(n_cols x T: E[x_t | y_1:T] and the uncorrected variance under exp_norm of the final weights). A row
+of `paths` picked by the final weights is what `sample(state, 1)` draws. The call has the persistent
+route only and throws where `ssm_run!` would issue the statements. (Written against the C ABI; not
+run in this repository's checks, which have no Julia.)
+"""
+function ssm_run_smoothed!(state::HipState, spec::WsmcSsmSpec, data::AbstractVecOrMat; scheme=RESAMPLE_STRATIFIED,
+                           paths::Bool=true)
+    T = size(data, 1)
+    S = Int(spec.n_cols)
+    n = Ref{Int64}(0)
+    check(ccall((:wsmc_nparticles, libwsmc), Cint, (Ptr{Cvoid}, Ref{Int64}), state.store.ctx, n))
+    d = Vector{Float64}(vec(permutedims(reshape(Float64.(data), T, :))))   # row-major T x data_dim
+    ev = Ref{Float64}(0.0)
+    pa = paths ? Array{Float64}(undef, n[], S, T) : nothing                  # C's [T][n_cols][n]
+    mean = Matrix{Float64}(undef, S, T); var = Matrix{Float64}(undef, S, T)   # C's [T][n_cols]
+    GC.@preserve pa mean var begin
+        sm = WsmcSsmSmooth(pa === nothing ? C_NULL : pointer(pa), pointer(mean), pointer(var))
+        check(ccall((:wsmc_ssm_run_smoothed, libwsmc), Cint,
+                    (Ptr{Cvoid}, Ref{WsmcSsmSpec}, Ptr{Float64}, Int32, Float64, Int32, Ptr{Float64}, Ptr{Cvoid},
+                     Ref{WsmcSsmSmooth}),
+                    state.store.ctx, spec, d, T, state.ess_perc_min, scheme, ev, C_NULL, sm))
+    end
+    mirror_flags!(state)
+    return ev[], (paths=pa, mean=mean, var=var)
+end
+
+"""
+    ssm_run_batch_smoothed(state, specs, data, n, seeds; scheme, paths=false)
+
+`ssm_run_batch` with every filter's smoothed output (`wsmc_ssm_run_batch_smoothed`): the named tuple
+also holds `smean` and `svar` (n_cols x T x B), `log_weights` (n x B) and, with `paths`, `paths`
+(n x n_cols x T x B). (Written against the C ABI; not run in this repository's checks, which have
+no Julia.)
+"""
+function ssm_run_batch_smoothed(state::HipState, specs, data, n::Integer, seeds::AbstractVector{<:Integer};
+                                scheme=RESAMPLE_STRATIFIED, paths::Bool=false)
+    B = length(seeds)
+    sp = specs isa WsmcSsmSpec ? [specs] : collect(WsmcSsmSpec, specs)
+    tabs = data isa AbstractVector{<:AbstractVecOrMat} ? collect(data) : [data]
+    length(sp) in (1, B) && length(tabs) in (1, B) || throw(ArgumentError("one spec / table, or one per filter"))
+    T = size(tabs[1], 1)
+    all(t -> size(t, 1) == T, tabs) || throw(ArgumentError("the filters' tables must have one length"))
+    rowmajor(t) = Vector{Float64}(vec(permutedims(reshape(Float64.(t), T, :))))
+    d = reduce(vcat, rowmajor.(tabs))
+    S = Int(sp[1].n_cols)
+    ev = Vector{Float64}(undef, B); nres = Vector{Int64}(undef, B); last = Vector{Int32}(undef, B)
+    lw = Matrix{Float64}(undef, n, B)
+    mean = Array{Float64}(undef, S, T, B); var = Array{Float64}(undef, S, T, B)
+    pa = paths ? Array{Float64}(undef, n, S, T, B) : nothing
+    sd = Vector{UInt64}(seeds .% UInt64)
+    GC.@preserve ev nres last lw mean var pa begin
+        out = WsmcSsmBatchOut(pointer(ev), C_NULL, C_NULL, pointer(lw), C_NULL, pointer(nres), pointer(last))
+        sm = WsmcSsmSmooth(pa === nothing ? C_NULL : pointer(pa), pointer(mean), pointer(var))
+        check(ccall((:wsmc_ssm_run_batch_smoothed, libwsmc), Cint,
+                    (Ptr{Cvoid}, Ptr{WsmcSsmSpec}, Int32, Ptr{Float64}, Int32, Int32, Int32, Int32, Ptr{UInt64},
+                     Float64, Int32, Ref{WsmcSsmBatchOut}, Ptr{Cvoid}, Ref{WsmcSsmSmooth}),
+                    state.store.ctx, sp, length(sp), isempty(d) ? C_NULL : d, length(tabs), T, n, B, sd,
+                    state.ess_perc_min, scheme, out, C_NULL, sm))
+    end
+    return (log_evidence=ev, n_resamples=nres, last_resampled=last .!= 0, smean=mean, svar=var, paths=pa, log_weights=lw)
+end
+
 end # module

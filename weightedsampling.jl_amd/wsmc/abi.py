@@ -125,6 +125,11 @@ class SsmTraceOut(C.Structure):
                 ("var", C.POINTER(C.c_double)), ("log_evidence", C.POINTER(C.c_double))]
 
 
+class SsmSmoothOut(C.Structure):
+    """wsmc_ssm_smooth: caller-owned host buffers of the smoothed output (NULL: not wanted)"""
+    _fields_ = [("paths", C.POINTER(C.c_double)), ("mean", C.POINTER(C.c_double)), ("var", C.POINTER(C.c_double))]
+
+
 class RunTiming(C.Structure):
     _fields_ = [("total_ms", C.c_double), ("propagate_ms", C.c_double),
                 ("reduce_ms", C.c_double), ("resample_ms", C.c_double),
@@ -210,6 +215,13 @@ SIGNATURES = {
     "wsmc_ssm_run_batch_traced": (C.c_int, [_P, C.POINTER(SsmSpec), C.c_int32, _D, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                             C.POINTER(C.c_uint64), C.c_double, C.c_int32, C.POINTER(SsmBatchOut),
                                             C.POINTER(SsmTraceOut)]),
+    "wsmc_ssm_smooth_sizeof": (C.c_int, [C.POINTER(C.c_int64)]),
+    "wsmc_debug_ssm_smooth": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "wsmc_ssm_run_smoothed": (C.c_int, [_P, C.POINTER(SsmSpec), _D, C.c_int32, C.c_double, C.c_int32, _D,
+                                        C.POINTER(SsmTraceOut), C.POINTER(SsmSmoothOut)]),
+    "wsmc_ssm_run_batch_smoothed": (C.c_int, [_P, C.POINTER(SsmSpec), C.c_int32, _D, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                              C.POINTER(C.c_uint64), C.c_double, C.c_int32, C.POINTER(SsmBatchOut),
+                                              C.POINTER(SsmTraceOut), C.POINTER(SsmSmoothOut)]),
     "wsmc_run_set_timing": (C.c_int, [_P, C.c_int32]),
     "wsmc_run_get_timing": (C.c_int, [_P, C.POINTER(RunTiming)]),
     "wsmc_debug_kernel_bench": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _D]),

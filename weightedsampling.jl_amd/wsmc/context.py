@@ -15,7 +15,7 @@ import numpy as np
 
 from . import abi
 from .abi import Dist, Operand, RunTiming, State, check, load_library
-from .ssm import SsmTrace, batch_arguments
+from .ssm import SsmSmooth, SsmTrace, batch_arguments, smooth_parts
 
 _D = C.POINTER(C.c_double)
 _I32P = C.POINTER(C.c_int32)
@@ -37,9 +37,11 @@ class SsmBatchResult:
     """What Context.ssm_run_batch returns: [B] arrays log_evidence, n_resamples, last_resampled;
     ess [B, T] when the trace was asked for; cols (name -> [B, n]), log_weights and last_ancestors
     [B, n] when the state was (None otherwise); with trace=True also mean and var (name -> [B, T])
-    and log_evidence_trace [B, T], each filter's SsmTrace rows."""
+    and log_evidence_trace [B, T], each filter's SsmTrace rows; with smooth also paths (name ->
+    [B, T, n]), smean and svar (name -> [B, T]), each filter's SsmSmooth."""
     log_evidence = n_resamples = last_resampled = ess = cols = log_weights = last_ancestors = None
     mean = var = log_evidence_trace = None
+    paths = smean = svar = None
 
 
 class Context:
@@ -475,7 +477,7 @@ class Context:
         check(self._L.wsmc_debug_lgssm(self._h, int(steps), None))
 
     def ssm_run(self, spec, data, ess_perc_min=1.0, scheme: int = abi.RESAMPLE_STRATIFIED,
-                want_evidence: bool = True, ess_trace: bool = False, T: int | None = None, trace=False):
+                want_evidence: bool = True, ess_trace: bool = False, T: int | None = None, trace=False, smooth=False):
         """A scalar state-space model (wsmc.SSM) as one call (wsmc_ssm_run): the same columns,
         weights, ancestors, state, tape and RNG positions as spec.statements(self, data, ...).
         data: T values, or T rows of the spec's data columns (a spec that reads no data takes T).
@@ -485,13 +487,21 @@ class Context:
         column's filtered mean and variance and the cumulative log evidence, bit for bit those of
         spec.statements(self, data, trace=True); everything else the run leaves is the untraced
         run's. trace may also name the parts wanted: a subset of ("ess", "mean", "var",
-        "log_evidence"); the others are None."""
+        "log_evidence"); the others are None.
+        smooth=True (wsmc_ssm_run_smoothed) returns (evidence, SsmSmooth), with trace as well
+        (evidence, SsmTrace, SsmSmooth): the final particles' trajectories and the smoothed moments,
+        bit for bit those of spec.statements(self, data, smooth=True). smooth may name the parts
+        wanted: a subset of ("paths", "mean", "var"). A smoothed run has the persistent route only:
+        what would send ssm_run through the statements raises WSMCError(WSMC_EARG) here."""
         tab = spec.table(data, T)
         ev = C.c_double()
-        if trace:
+        sparts = smooth_parts(smooth)
+        if sparts and ess_trace:
+            raise ValueError("ess_trace and smooth: ask for the ESS% with trace=(\"ess\",)")
+        if trace or sparts:
             if ess_trace:
                 raise ValueError("ess_trace and trace: the trace holds the ESS% (SsmTrace.ess)")
-            parts = ("ess", "mean", "var", "log_evidence") if trace is True else tuple(trace)
+            parts = ("ess", "mean", "var", "log_evidence") if trace is True else tuple(trace or ())
             bad = [p for p in parts if p not in ("ess", "mean", "var", "log_evidence")]
             if bad:
                 raise ValueError(f"trace: unknown part {bad[0]!r}")
@@ -501,14 +511,27 @@ class Context:
             out = abi.SsmTraceOut()
             for p in parts:
                 setattr(out, p, _dptr(buf[p]))
-            check(self._L.wsmc_ssm_run_traced(self._h, C.byref(spec.spec), _dptr(tab) if tab.size else None, steps,
-                                              float(ess_perc_min), int(scheme), C.byref(ev) if want_evidence else None,
-                                              C.byref(out)))
             by_name = lambda a: {c: a[:, k].copy() for k, c in enumerate(spec.cols)}
+            head = (self._h, C.byref(spec.spec), _dptr(tab) if tab.size else None, steps, float(ess_perc_min), int(scheme),
+                    C.byref(ev) if want_evidence else None, C.byref(out))
+            if sparts:
+                sbuf = {"paths": np.empty((steps, S, self.n)) if "paths" in sparts else None,
+                        "mean": np.empty((steps, S)) if "mean" in sparts else None,
+                        "var": np.empty((steps, S)) if "var" in sparts else None}
+                so = abi.SsmSmoothOut()
+                for p in sparts:
+                    setattr(so, p, _dptr(sbuf[p]))
+                check(self._L.wsmc_ssm_run_smoothed(*head, C.byref(so)))
+                sm = SsmSmooth({c: sbuf["paths"][:, k, :] for k, c in enumerate(spec.cols)} if "paths" in sparts else None,
+                               by_name(sbuf["mean"]) if "mean" in sparts else None,
+                               by_name(sbuf["var"]) if "var" in sparts else None, self.weights_download())
+            else:
+                check(self._L.wsmc_ssm_run_traced(*head))
             tr = SsmTrace(buf["ess"] if "ess" in parts else None, by_name(buf["mean"]) if "mean" in parts else None,
                           by_name(buf["var"]) if "var" in parts else None,
                           buf["log_evidence"] if "log_evidence" in parts else None)
-            return (float(ev.value) if want_evidence else None), tr
+            res = ((float(ev.value) if want_evidence else None),) + ((tr,) if trace else ()) + ((sm,) if sparts else ())
+            return res
         tr = np.empty(len(tab)) if ess_trace else None
         check(self._L.wsmc_ssm_run(self._h, C.byref(spec.spec), _dptr(tab) if tab.size else None, len(tab),
                                    float(ess_perc_min), int(scheme), C.byref(ev) if want_evidence else None,
@@ -533,7 +556,7 @@ class Context:
 
     def ssm_run_batch(self, specs, data, n: int, seeds, ess_perc_min=1.0, scheme: int = abi.RESAMPLE_STRATIFIED,
                       ess_trace: bool = False, state: bool = False, T: int | None = None,
-                      trace: bool = False) -> "SsmBatchResult":
+                      trace: bool = False, smooth=False) -> "SsmBatchResult":
         """B = len(seeds) independent filters of n particles in one call (wsmc_ssm_run_batch), one
         persistent workgroup each: filter b is, bit for bit, ssm_run(spec b, table b) on a fresh
         Context(n, seed=seeds[b]). This context gives the device and the stream; its own particles
@@ -544,7 +567,11 @@ class Context:
         ess_trace `ess` [B, T], with state `cols` (name -> [B, n]), `log_weights` [B, n] and
         `last_ancestors` [B, n] (row b is zeros while filter b has not resampled). trace=True
         (wsmc_ssm_run_batch_traced) also fills `ess`, `mean` / `var` (name -> [B, T]) and
-        `log_evidence_trace` [B, T]: row b is ssm_run(trace=True)'s SsmTrace of filter b."""
+        `log_evidence_trace` [B, T]: row b is ssm_run(trace=True)'s SsmTrace of filter b.
+        smooth=True, or a subset of ("paths", "mean", "var") (wsmc_ssm_run_batch_smoothed), fills
+        `paths` (name -> [B, T, n]), `smean` and `svar` (name -> [B, T]): row b is
+        ssm_run(smooth=True)'s SsmSmooth of filter b (its log_weights are `log_weights` with state)."""
+        sparts = smooth_parts(smooth)
         spec_list, tabs, seeds_a = batch_arguments(specs, data, n, seeds, T)   # (before any device call)
         B, first, steps = len(seeds_a), spec_list[0], len(tabs[0])
         tab = np.ascontiguousarray(np.stack(tabs)) if tabs[0].size else None
@@ -572,23 +599,46 @@ class Context:
             out.last_ancestors = res.last_ancestors.ctypes.data_as(_I32P)
         args = (self._h, arr, len(spec_list), _dptr(tab) if tab is not None else None, len(tabs), steps, int(n), B,
                 seeds_a.ctypes.data_as(C.POINTER(C.c_uint64)), float(ess_perc_min), int(scheme), C.byref(out))
+        tr = abi.SsmTraceOut()
         if trace:
-            tr = abi.SsmTraceOut()
             mean, var = np.empty((B, steps, S)), np.empty((B, steps, S))
             res.log_evidence_trace = np.empty((B, steps))
             if res.ess is None:
                 res.ess = np.empty((B, steps))
             tr.ess, tr.mean, tr.var = _dptr(res.ess), _dptr(mean), _dptr(var)
             tr.log_evidence = _dptr(res.log_evidence_trace)
+        if sparts:
+            so = abi.SsmSmoothOut()
+            sbuf = {"paths": np.empty((B, steps, S, int(n))) if "paths" in sparts else None,
+                    "mean": np.empty((B, steps, S)) if "mean" in sparts else None,
+                    "var": np.empty((B, steps, S)) if "var" in sparts else None}
+            for p in sparts:
+                setattr(so, p, _dptr(sbuf[p]))
+            check(self._L.wsmc_ssm_run_batch_smoothed(*args, C.byref(tr), C.byref(so)))
+            if "paths" in sparts:
+                res.paths = {name: sbuf["paths"][:, :, k, :] for k, name in enumerate(first.cols)}
+            if "mean" in sparts:
+                res.smean = {name: sbuf["mean"][:, :, k].copy() for k, name in enumerate(first.cols)}
+            if "var" in sparts:
+                res.svar = {name: sbuf["var"][:, :, k].copy() for k, name in enumerate(first.cols)}
+        elif trace:
             check(self._L.wsmc_ssm_run_batch_traced(*args, C.byref(tr)))
-            res.mean = {name: mean[:, :, k].copy() for k, name in enumerate(first.cols)}
-            res.var = {name: var[:, :, k].copy() for k, name in enumerate(first.cols)}
         else:
             check(self._L.wsmc_ssm_run_batch(*args))
+        if trace:
+            res.mean = {name: mean[:, :, k].copy() for k, name in enumerate(first.cols)}
+            res.var = {name: var[:, :, k].copy() for k, name in enumerate(first.cols)}
         res.last_resampled = res.last_resampled.astype(bool)
         if state:
             res.cols = {name: cols[:, k, :] for k, name in enumerate(first.cols)}
         return res
+
+    def ssm_smooth_stats(self) -> dict:
+        """wsmc_debug_ssm_smooth's figures of the last smoothed run or batch on this context: device
+        seconds of its segments, of the trace-back and of the rows kernel, and the bytes of the log."""
+        st = (C.c_int64 * 4)()
+        check(self._L.wsmc_debug_ssm_smooth(self._h, st))
+        return {"segments_s": st[0] / 1e6, "traceback_s": st[1] / 1e6, "rows_s": st[2] / 1e6, "log_bytes": int(st[3])}
 
     def ssm_batch_stats(self) -> dict:
         """wsmc_debug_ssm_batch's figures: the last batch's resident workgroups per CU, the device's

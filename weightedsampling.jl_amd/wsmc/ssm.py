@@ -76,6 +76,18 @@ def batch_arguments(specs, data, n, seeds, T=None):
     return spec_list, tabs, seeds_a
 
 
+def smooth_parts(smooth) -> tuple:
+    """Context.ssm_run's `smooth` argument as the parts wanted: () for a false value, all three for
+    True, else the names given (ValueError for one that is none of them)"""
+    if not smooth:
+        return ()
+    parts = ("paths", "mean", "var") if smooth is True else ((smooth,) if isinstance(smooth, str) else tuple(smooth))
+    bad = [p for p in parts if p not in ("paths", "mean", "var")]
+    if bad:
+        raise ValueError(f"smooth: unknown part {bad[0]!r}")
+    return parts
+
+
 class SsmTrace:
     """The per-step filtering trace of a scalar-SSM run (include/wsmc.h wsmc_ssm_trace). Row t is
     taken after step t's last observe, before the Resample that follows it: `ess` [T] that
@@ -89,6 +101,33 @@ class SsmTrace:
     def predictive_loglik(self) -> np.ndarray:
         """log p(y_t | y_1:t-1), t = 0 .. T-1: the first difference of log_evidence"""
         return np.diff(self.log_evidence, prepend=0.0)
+
+
+class SsmSmooth:
+    """The smoothed output of a scalar-SSM run (include/wsmc.h wsmc_ssm_smooth): the genealogy of
+    the final particles traced back through every resampling step. `paths` (column name -> [T, N]):
+    paths[name][t][i] is the column's value at trace point t (after step t's last observe, before
+    the Resample that follows it) of final particle i's ancestor; `mean` / `var` (name -> [T]):
+    E[x_t | y_1:T] and the uncorrected variance under exp_norm of the final weights
+    (Context.weighted_moments of row t); `log_weights` [N], the final ones. A part that was not
+    asked for is None."""
+
+    def __init__(self, paths, mean, var, log_weights):
+        self.paths, self.mean, self.var, self.log_weights = paths, mean, var, log_weights
+
+    def draw(self, k: int, rng=None) -> dict:
+        """k posterior trajectories (name -> [k, T]), picked with replacement by exp_norm of the
+        final weights on the host: the analogue of the reference's sample(state, k)"""
+        if self.paths is None:
+            raise ValueError("draw: the paths were not asked for")
+        rng = np.random.default_rng() if rng is None else rng
+        lw = np.asarray(self.log_weights, dtype=np.float64)
+        w = np.exp(lw - np.max(lw))
+        idx = rng.choice(len(w), size=int(k), p=w / w.sum())
+        return {name: p[:, idx].T.copy() for name, p in self.paths.items()}
+
+
+STORE_COLUMNS = 4096   # the columns one context's store holds
 
 
 class SSM:
@@ -217,7 +256,7 @@ class SSM:
 
     # ---- the executable definition ----
     def statements(self, backend, data, ess_perc_min: float = 1.0, scheme: int = abi.RESAMPLE_STRATIFIED,
-                   wait: bool = True, T: int | None = None, trace: bool = False):
+                   wait: bool = True, T: int | None = None, trace: bool = False, smooth: bool = False):
         """Issue the spec's statements one by one on `backend` (a Context or the tests' Oracle: any
         object with the operator methods), each `sample` / `observe` followed by its Resample, the
         step's data folded into constants: a data slot of an operand is removed and its value
@@ -226,12 +265,20 @@ class SSM:
         wait=False leaves every Resample asynchronous and returns None. trace=True (with wait)
         also takes backend.weighted_moments of every column and backend.log_evidence() between each
         step's last observe and its Resample and returns (flags, ESS%, SsmTrace): the definition
-        of what Context.ssm_run(trace=True) returns."""
+        of what Context.ssm_run(trace=True) returns. smooth=True (with wait) also keeps every
+        column's values at each trace point in a column of their own, `name@t`, which the Resamples
+        that follow gather like any other, and reads them after the last step: the result gains an
+        SsmSmooth as its last member, the definition of what Context.ssm_run(smooth=True) returns."""
         if trace and not wait:
             raise ValueError("trace=True needs wait=True (the trace point is a synchronisation)")
+        if smooth and not wait:
+            raise ValueError("smooth=True needs wait=True (the trace point is a synchronisation)")
         sp = self.spec
         tab = self.table(data, T)
         T = len(tab)
+        if smooth and T * len(self.cols) + len(self.cols) > STORE_COLUMNS:
+            raise ValueError(f"smooth=True: {T} steps of {len(self.cols)} columns need {T * len(self.cols) + len(self.cols)} "
+                             f"store columns (at most {STORE_COLUMNS})")
         ids = [backend.col_create(name, 1) for name in self.cols]
 
         # every statement is built once (ids mapped, data slots removed); a step only writes its
@@ -310,25 +357,44 @@ class SSM:
             mean, var, lev = np.empty((T, S)), np.empty((T, S)), np.empty(T)
             exprs = [Operand.column(ids[k]) for k in range(S)]
 
+        hist = []   # smooth: step t's history columns, in the spec's order
+
         def point(t):
-            m, cv = backend.weighted_moments(exprs)
-            mean[t], var[t] = m, np.diagonal(cv)
-            lev[t] = backend.log_evidence()
+            if trace:
+                m, cv = backend.weighted_moments(exprs)
+                mean[t], var[t] = m, np.diagonal(cv)
+                lev[t] = backend.log_evidence()
+            if smooth:
+                hs = [backend.col_create(f"{name}@{t}", 1) for name in self.cols]
+                for h, i in zip(hs, ids):
+                    backend.assign(h, [Operand.column(i)])
+                hist.append(hs)
 
         for t in range(T):
             row = tab[t]
             for q, (call, patch) in enumerate(step):
                 for obj, field, j in patch:
                     setattr(obj, field, row[j])
-                if trace and q == last:
+                if (trace or smooth) and q == last:
                     r = call(True, lambda: point(t))
                 else:
                     r = call(wait and q == last)
                 if wait and q == last:
                     flags.append(bool(r[0]))
                     ess.append(float(r[1]))
+        out = (flags, np.array(ess)) if wait else None
         if trace:
             tr = SsmTrace(np.array(ess), {c: mean[:, k].copy() for k, c in enumerate(self.cols)},
                           {c: var[:, k].copy() for k, c in enumerate(self.cols)}, lev)
-            return flags, tr.ess, tr
-        return (flags, np.array(ess)) if wait else None
+            out = (flags, tr.ess, tr)
+        if smooth:
+            n_cols = len(self.cols)
+            paths = {c: np.stack([backend.col_download(hist[t][k]) for t in range(T)]) for k, c in enumerate(self.cols)}
+            smean, svar = np.empty((T, n_cols)), np.empty((T, n_cols))
+            for t in range(T):
+                m, cv = backend.weighted_moments([Operand.column(h) for h in hist[t]])
+                smean[t], svar[t] = m, np.diagonal(cv)
+            sm = SsmSmooth(paths, {c: smean[:, k].copy() for k, c in enumerate(self.cols)},
+                           {c: svar[:, k].copy() for k, c in enumerate(self.cols)}, backend.weights_download())
+            out = out + (sm,)
+        return out
