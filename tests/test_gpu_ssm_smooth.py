@@ -228,6 +228,14 @@ def test_null_smooth_is_the_traced_run():
     o.close()
 
 
+def _before_the_run(c, foreign=False, weights=False):
+    """what a context holds when a reason against the persistent route lies in its state"""
+    if foreign:
+        c.assign(c.col_create("other", 1), [abi.Operand.const(0.3)])
+    if weights:
+        c.observe(models.sv().spec.init[0].dist, [abi.Operand.const(0.1)])
+
+
 def test_refusals_leave_the_context_as_it_was(cap):
     """a smoothed run has the persistent route only: what sends ssm_run through the statements raises
     here, before anything of the context changes (not even the spec's columns are made)"""
@@ -237,10 +245,7 @@ def test_refusals_leave_the_context_as_it_was(cap):
         g, o = wsmc.Context(n, seed=5), Oracle(n, seed=5)
         try:
             for c in (g, o):
-                if foreign:
-                    c.assign(c.col_create("other", 1), [abi.Operand.const(0.3)])
-                if weights:
-                    c.observe(models.sv().spec.init[0].dist, [abi.Operand.const(0.1)])
+                _before_the_run(c, foreign, weights)
             with pytest.raises(wsmc.WSMCError) as e:
                 g.ssm_run(ssm, data, ess_perc_min=0.5, scheme=scheme, smooth=True)
             assert e.value.code == abi.WSMC_EARG and word in str(e.value), str(e.value)
@@ -266,6 +271,35 @@ def test_refusals_leave_the_context_as_it_was(cap):
     with pytest.raises(wsmc.WSMCError, match="multi-device"):
         m.ssm_run(ssm, data, smooth=True)
     m.close()
+
+
+# each single-device reason of the refusals above: (word, n or "cap", the call's scheme, the context's state)
+ROUTE_REASONS = [("above the cap", "cap", STRAT, {}), ("not the spec's", 65, STRAT, dict(foreign=True)),
+                 ("multinomial", 65, MULT, {}), ("weights_changed", 65, STRAT, dict(weights=True)),
+                 ("program instructions", 65, STRAT, {}), (None, 65, STRAT, {})]
+
+
+@pytest.mark.parametrize("word,n,scheme,state", ROUTE_REASONS, ids=[r[0] or "no reason" for r in ROUTE_REASONS])
+def test_what_refuses_a_smoothed_run_sends_an_untraced_one_through_the_statements(cap, word, n, scheme, state):
+    """the route rule is stated once: on a context set up exactly as the refused smoothed call's
+    was, the untraced ssm_run is one statement run and no persistent one; with no reason present
+    the same call is one persistent run and no statement run. T = 4"""
+    if word == "program instructions":
+        big = sf.gen("prog97", "directed")
+        ssm, data, ess = big.ssm, big.data[:4], 1.0
+    else:
+        ssm, data, ess = SPECS["sv"][0], SPECS["sv"][1][:4], 0.5
+    g = wsmc.Context(cap[len(ssm.cols)] + 1 if n == "cap" else n, seed=5)
+    try:
+        _before_the_run(g, **state)
+        if word is not None:   # ... and the smoothed call is refused for this reason
+            with pytest.raises(wsmc.WSMCError, match=word):
+                g.ssm_run(ssm, data, ess_perc_min=ess, scheme=scheme, smooth=True)
+        g.ssm_run(ssm, data, ess_perc_min=ess, scheme=scheme)
+        st = g.ssm_stats()
+        assert (st["persistent_runs"], st["statement_runs"]) == ((1, 0) if word is None else (0, 1)), (word, st)
+    finally:
+        g.close()
 
 
 def test_untraced_and_traced_runs_after_a_smoothed_one():

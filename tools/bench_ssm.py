@@ -84,7 +84,7 @@ def child(leg: str, T: int) -> dict:
         st = ctx.ssm_stats()
         assert st["persistent_runs"] == 1, st
         ex = {"log_evidence": ctx.log_evidence(), "resamples": ctx.get_state()["n_resamples"],
-              "host_bookkeeping_s": st["bookkeeping_s"], "segments": st["segments"]}
+              "host_bookkeeping_s": st["bookkeeping_s"], "host_call_s": st["call_s"], "segments": st["segments"]}
         ctx.close()
         return dt, ex
 
@@ -133,7 +133,7 @@ def child(leg: str, T: int) -> dict:
            "statements_s": s, "statements_us_per_step": 1e6 * s / T,
            "statements_lib_s": sl, "statements_lib_us_per_step": 1e6 * sl / T,
            "factor_vs_statements": s / p, "factor_vs_statements_lib": sl / p,
-           "host_bookkeeping_s": pe["host_bookkeeping_s"], "segments": pe["segments"],
+           "host_bookkeeping_s": pe["host_bookkeeping_s"], "host_call_s": pe["host_call_s"], "segments": pe["segments"],
            "log_evidence": pe["log_evidence"]}
     if leg == "lgssm":
         k, ke = best_of(lgssm_kernel)

@@ -5168,6 +5168,51 @@ int wsmc_debug_kernel_bench(wsmc_ctx* c, int32_t kernel, int32_t mode, int32_t i
     return WSMC_OK;
 }
 
+// ---- what the persistent-workgroup runs share (wsmc_lgssm1d_run, wsmc_ssm_run, wsmc_ssm_run_batch) ----
+using clk = std::chrono::steady_clock;
+static int64_t us(clk::time_point t0, clk::time_point t1) {
+    return (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count();
+}
+// a buffer of the context, grown to `need` doubles where it is smaller (the stream may still read it)
+static int ctx_grow(wsmc_ctx* c, double** p, int64_t* cap, int64_t need) {
+    if (*cap >= need) return WSMC_OK;
+    WSMC_HIP(ctx_sync(c, c->stream));
+    if (*p) WSMC_HIP(hipFree(*p));
+    *p = nullptr;
+    *cap = 0;
+    WSMC_HIP(hipMalloc(p, sizeof(double) * (size_t)need));
+    *cap = need;
+    return WSMC_OK;
+}
+// a persistent run's way in. stored: the run reads columns, so those a lazy Resample left behind are stored first
+static int persistent_enter(wsmc_ctx* c, bool stored) {
+    CHECK_CTX(c);   // an asynchronous run, the open statement batch, unstored Samples, a pending reset
+    if (int rc = resolve_decisions(c)) return rc;
+    if (int rc = check_deferred(c)) return rc;
+    scores_invalidate(c);   // the run rewrites the columns the tape reads
+    if (stored)
+        if (int rc = materialize(c, nullptr)) return rc;
+    c->wseq += 1;           // ... and the weights
+    return WSMC_OK;
+}
+// ... and its record into the context, after the stream's end
+static void persistent_leave(wsmc_ctx* c, const LgRecord& r) {
+    c->resampled = r.last_dec;
+    c->last_ess = r.last_ess;
+    c->n_resamples += r.nres;
+    if (r.nres) set_anc_last(c, nullptr, -1);   // the last resampling step's row is in c->anc
+    c->wseq += 1;
+}
+// the segment [t0, t0 + K) of a run of T steps, in its launch's arguments
+extern "C++" {   // (a template inside the entry points' extern "C")
+template <class Args>
+static void set_segment(Args& ka, int32_t t0, int32_t K, int32_t T) {
+    ka.t0 = t0;
+    ka.nsteps = std::min<int32_t>(K, T - t0);
+    ka.first = t0 == 0;
+}
+}
+
 // ---- fused 1D LGSSM run (csrc/wsmc_lgssm.hip) ------------------------------------------------
 // Normal(c0 + coef * col, sigma) as wsmc.dsl's Normal(...).dist builds it (col < 0: Normal(0, sigma))
 static wsmc_dist lg_normal(int32_t col, double coef, double sigma) {
@@ -5221,10 +5266,6 @@ int wsmc_lgssm1d_run(wsmc_ctx* c, const double* data, int32_t T, double a, doubl
     if (!data || T < 1) return fail(WSMC_EARG, "bad arguments");
     if (!(q > 0) || !(r > 0) || !(x0_std > 0)) return fail(WSMC_EARG, "standard deviations must be positive");
     if (!valid_scheme(scheme)) return fail(WSMC_EARG, "unknown resampling scheme");
-    using clk = std::chrono::steady_clock;
-    auto us = [](clk::time_point t0, clk::time_point t1) {
-        return (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count();
-    };
     const auto t_in = clk::now();
     wsmc_ctx* sc = c->multi ? multi_first(c) : c;   // the counters' holder
     // the persistent workgroup: one unsharded context, N within the cap, a stratified / systematic
@@ -5241,29 +5282,12 @@ int wsmc_lgssm1d_run(wsmc_ctx* c, const double* data, int32_t T, double a, doubl
         sc->lg_wall_us = us(t_in, clk::now());
         return WSMC_OK;
     }
-    CHECK_CTX(c);   // an asynchronous run, the open statement batch, unstored Samples, a pending reset
-    if (int rc = resolve_decisions(c)) return rc;
-    if (int rc = check_deferred(c)) return rc;
-    scores_invalidate(c);   // the run rewrites the column the tape reads
-    c->wseq += 1;           // ... and the weights
+    if (int rc = persistent_enter(c, false)) return rc;
     int32_t cx = -1;
     if (int rc = wsmc_col_create(c, "x", 1, &cx)) return rc;
-    if (c->lg_data_cap < T) {
-        WSMC_HIP(ctx_sync(c, c->stream));
-        if (c->lg_data) WSMC_HIP(hipFree(c->lg_data));
-        c->lg_data = nullptr;
-        c->lg_data_cap = 0;
-        WSMC_HIP(hipMalloc(&c->lg_data, sizeof(double) * (size_t)T));
-        c->lg_data_cap = T;
-    }
-    if (ess_trace_out && c->lg_trace_cap < T) {
-        WSMC_HIP(ctx_sync(c, c->stream));
-        if (c->lg_trace) WSMC_HIP(hipFree(c->lg_trace));
-        c->lg_trace = nullptr;
-        c->lg_trace_cap = 0;
-        WSMC_HIP(hipMalloc(&c->lg_trace, sizeof(double) * (size_t)T));
-        c->lg_trace_cap = T;
-    }
+    if (int rc = ctx_grow(c, &c->lg_data, &c->lg_data_cap, T)) return rc;
+    if (ess_trace_out)
+        if (int rc = ctx_grow(c, &c->lg_trace, &c->lg_trace_cap, T)) return rc;
     if (!c->lg_rec) WSMC_HIP(hipMalloc(&c->lg_rec, sizeof(LgRecord)));
     WSMC_HIP(hipMemcpyAsync(c->lg_data, data, sizeof(double) * (size_t)T, hipMemcpyHostToDevice, c->stream));
     WSMC_HIP(hipMemsetAsync(c->lg_rec, 0, sizeof(LgRecord), c->stream));
@@ -5294,9 +5318,7 @@ int wsmc_lgssm1d_run(wsmc_ctx* c, const double* data, int32_t T, double a, doubl
     const int32_t K = c->lg_segment > 0 ? c->lg_segment : kLgSegmentSteps;
     int64_t nseg = 0;
     for (int32_t t0 = 0; t0 < T; t0 += K, ++nseg) {
-        ka.t0 = t0;
-        ka.nsteps = std::min<int32_t>(K, T - t0);
-        ka.first = t0 == 0;
+        set_segment(ka, t0, K, T);
         WSMC_HIP(launch_lgssm_segment(c->stream, ka, threads));
     }
     LgRecord hrec;
@@ -5330,11 +5352,7 @@ int wsmc_lgssm1d_run(wsmc_ctx* c, const double* data, int32_t T, double a, doubl
     c->weights_changed = 0;
     const auto t_booked = clk::now();
     WSMC_HIP(ctx_sync(c, c->stream));
-    c->resampled = hrec.last_dec;
-    c->last_ess = hrec.last_ess;
-    c->n_resamples += hrec.nres;
-    if (hrec.nres) set_anc_last(c, nullptr, -1);   // the last resampling step's row is in c->anc
-    c->wseq += 1;
+    persistent_leave(c, hrec);
     c->lg_runs += 1;
     c->lg_segments += nseg;
     c->lg_book_us = us(t_book, t_booked);
@@ -5471,16 +5489,32 @@ static wsmc_dist ssm_map_dist(const wsmc_dist& d, const int32_t* ids, const doub
     r.scale = ssm_map_operand(d.scale, ids, row);
     return r;
 }
-static int ssm_op_count(const wsmc_ssm_stmt* s, int n) {   // 2 a SAMPLE (its Resample's too), 1 an OBSERVE
-    int ops = 0;
-    for (int q = 0; q < n; ++q) ops += s[q].kind == WSMC_SSM_SAMPLE ? 2 : s[q].kind == WSMC_SSM_OBSERVE ? 1 : 0;
-    return ops;
-}
-static int ssm_last_observe(const wsmc_ssm_spec* sp) {
-    int last = -1;
-    for (int q = 0; q < sp->n_step; ++q)
-        if (sp->step[q].kind == WSMC_SSM_OBSERVE) last = q;
-    return last;
+// What a (checked) spec is, counted in one pass: every size, count and route decision of the runs
+// below reads this, so a new per-spec fact goes here
+struct SsmShape {
+    int S, data_dim, n_init, n_step;
+    int nprog;                    // program instructions over the whole spec
+    unsigned feat;                // WSMC_FEAT_ bits over its dists (the kernel's instantiation)
+    int n_obs, last_obs;          // a step's OBSERVEs, and the last one (its Resample's ESS% is the trace's)
+    int init_ops, step_ops;       // op counters `init` / one step take: 2 a SAMPLE (its Resample's too), 1 an OBSERVE
+    int init_terms, step_terms;   // tape terms `init` / one step leave: one a SAMPLE, one an OBSERVE
+};
+static SsmShape ssm_shape(const wsmc_ssm_spec* sp) {
+    SsmShape h = {sp->n_cols, sp->data_dim, sp->n_init, sp->n_step, 0, 0u, 0, -1, 0, 0, 0, 0};
+    for (int q = 0; q < sp->n_init + sp->n_step; ++q) {
+        const bool step = q >= sp->n_init;
+        const wsmc_ssm_stmt& s = step ? sp->step[q - sp->n_init] : sp->init[q];
+        const bool sample = s.kind == WSMC_SSM_SAMPLE, observe = s.kind == WSMC_SSM_OBSERVE;
+        if (s.kind == WSMC_SSM_ASSIGN_EXPR) h.nprog += s.prog_len;
+        if (sample || observe) h.feat |= wsmc_dist_feat(&s.dist);
+        (step ? h.step_ops : h.init_ops) += sample ? 2 : observe ? 1 : 0;
+        (step ? h.step_terms : h.init_terms) += sample || observe;
+        if (step && observe) {
+            h.n_obs += 1;
+            h.last_obs = q - sp->n_init;
+        }
+    }
+    return h;
 }
 
 // one statement through the operators, with its auto-inserted Resample. ess_out: wait on that
@@ -5550,15 +5584,15 @@ static int ssm_issue(wsmc_ctx* c, const wsmc_ssm_stmt& s, const int32_t* ids, co
 }
 // the statement route: the spec's statements as a loop over the operators (any handle, any N, any
 // scheme); it is the definition of the run's results
-static int ssm_statements(wsmc_ctx* c, const wsmc_ssm_spec* sp, const int32_t* ids, const double* data, int32_t T,
-                          double ess_min, int32_t scheme, const wsmc_ssm_trace& tr) {
+static int ssm_statements(wsmc_ctx* c, const wsmc_ssm_spec* sp, const SsmShape& sh, const int32_t* ids, const double* data,
+                          int32_t T, double ess_min, int32_t scheme, const wsmc_ssm_trace& tr) {
     double* ess_trace = tr.ess;
     const bool moms = tr.mean || tr.var || tr.log_evidence;
     const size_t S = (size_t)sp->n_cols;
     int rc;
     for (int q = 0; q < sp->n_init; ++q)
         if ((rc = ssm_issue(c, sp->init[q], ids, nullptr, ess_min, scheme, nullptr))) return rc;
-    const int last = ssm_last_observe(sp);
+    const int last = sh.last_obs;
     for (int32_t t = 0; t < T; ++t) {
         const double* row = data ? data + (size_t)t * sp->data_dim : nullptr;
         const SsmRowOut mom = {sp->n_cols, tr.mean ? tr.mean + t * S : nullptr, tr.var ? tr.var + t * S : nullptr,
@@ -5599,6 +5633,55 @@ static SsmStmt ssm_dev_stmt(const wsmc_ssm_stmt& s, SsmIns* ins, int* nins) {
     }
     return r;
 }
+// a spec's statements as the kernel reads them (a filter's parameter bits are the single run's)
+static void ssm_dev_image(const wsmc_ssm_spec* sp, SsmStmt* init, SsmStmt* step, SsmIns* ins) {
+    int nins = 0;
+    for (int q = 0; q < sp->n_init; ++q) init[q] = ssm_dev_stmt(sp->init[q], ins, &nins);
+    for (int q = 0; q < sp->n_step; ++q) step[q] = ssm_dev_stmt(sp->step[q], ins, &nins);
+}
+// the arguments SsmArgs and SsmBatchArgs share (a segment's own are set_segment's)
+extern "C++" {
+template <class Args>
+static void ssm_fill_args(Args& ka, const SsmShape& sh, int64_t n, int threads, int32_t scheme, double ess_min) {
+    ka.N = (int32_t)n;
+    ka.P = (int32_t)((n + threads - 1) / threads);
+    ka.S = sh.S;
+    ka.data_dim = sh.data_dim;
+    ka.scheme = scheme;
+    ka.n_init = sh.n_init;
+    ka.n_step = sh.n_step;
+    ka.init_ops = sh.init_ops;
+    ka.step_ops = sh.step_ops;
+    ka.last_obs = sh.last_obs;
+    ka.ess_min = ess_min;
+}
+}
+// steps a launch by default: kSsmSegmentStmts statements, fewer with more than two particles a thread
+static int32_t ssm_default_steps(const SsmShape& sh, int P) {
+    return std::max(1, kSsmSegmentStmts / sh.n_step * 2 / std::max(2, P));
+}
+// The persistent workgroup's conditions, stated once: the first reason a call of n particles cannot
+// take it, or empty. One unsharded context, n within the cap for S columns, a stratified /
+// systematic scheme and the programs within the kernel's arguments; with own_state (the single
+// run, which works on the context's particles) the weights unchanged (so a Resample after a SAMPLE
+// never runs) and no column but the spec's. A new condition goes here
+static std::string ssm_route_why(const wsmc_ctx* c, const wsmc_ssm_spec* sp, const SsmShape& sh, int64_t n, int32_t scheme,
+                                 bool own_state) {
+    if (c->multi || is_sharded(c)) return "a sharded or multi-device context (one unsharded device runs it)";
+    if (n > ssm_cap(sh.S))
+        return "n = " + std::to_string(n) + " above the cap of " + std::to_string(ssm_cap(sh.S)) + " particles for " +
+               std::to_string(sh.S) + " columns";
+    if (scheme == WSMC_RESAMPLE_MULTINOMIAL) return "multinomial resampling (the persistent workgroup has stratified and systematic)";
+    if (own_state && c->weights_changed) return "weights_changed is set (a Resample after a SAMPLE could run)";
+    if (sh.nprog > kSsmProgMax)
+        return std::to_string(sh.nprog) + " program instructions (more than " + std::to_string(kSsmProgMax) + ")";
+    for (size_t j = 0; own_state && j < c->cols.size(); ++j) {
+        bool in = false;
+        for (int k = 0; k < sh.S; ++k) in |= c->cols[j].name == sp->col_names[k];
+        if (!in) return "the context holds a column that is not the spec's (" + c->cols[j].name + ")";
+    }
+    return std::string();
+}
 
 int wsmc_ssm_trace_sizeof(int64_t* bytes) {
     if (!bytes) return fail(WSMC_EARG, "null argument");
@@ -5611,6 +5694,9 @@ int wsmc_ssm_smooth_sizeof(int64_t* bytes) {
     *bytes = (int64_t)sizeof(wsmc_ssm_smooth);
     return WSMC_OK;
 }
+// nothing wanted of either
+static const wsmc_ssm_trace kNoTrace = {nullptr, nullptr, nullptr, nullptr};
+static const wsmc_ssm_smooth kNoSmooth = {nullptr, nullptr, nullptr};
 
 // a call's device allocation, freed on return (hipFree waits for the device)
 struct SsmSlab {
@@ -5618,11 +5704,6 @@ struct SsmSlab {
     ~SsmSlab() { if (p) (void)hipFree(p); }
 };
 static size_t ssm_up(size_t v) { return (v + 255) & ~(size_t)255; }
-static int ssm_count_observes(const wsmc_ssm_spec* sp) {
-    int n = 0;
-    for (int q = 0; q < sp->n_step; ++q) n += sp->step[q].kind == WSMC_SSM_OBSERVE;
-    return n;
-}
 // A smoothed run's log for B filters of n particles, carved from `base` (null: the sizes alone):
 // the history, the ancestor log, its flags, then the smoothed rows where wanted. Returns the bytes
 struct SsmSmoothBufs {
@@ -5693,10 +5774,6 @@ static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int
     if (int rc = wsmc_ssm_spec_check(sp)) return rc;
     if (T < 1 || (sp->data_dim > 0 && !data)) return fail(WSMC_EARG, "bad arguments");
     if (!valid_scheme(scheme)) return fail(WSMC_EARG, "unknown resampling scheme");
-    using clk = std::chrono::steady_clock;
-    auto us = [](clk::time_point t0, clk::time_point t1) {
-        return (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count();
-    };
     const auto t_in = clk::now();
     wsmc_ctx* sc = c->multi ? multi_first(c) : c;   // the counters' holder
     const int S = sp->n_cols;
@@ -5708,57 +5785,30 @@ static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int
         if (int rc = wsmc_col_info(c, ids[k], nullptr, 0, &dim)) return rc;
         if (dim != 1) return fail(WSMC_EARG, std::string("ssm spec: column ") + sp->col_names[k] + " exists with dim != 1");
     }
-    int nprog = 0;
-    unsigned feat = 0;
-    for (int q = 0; q < sp->n_init + sp->n_step; ++q) {
-        const wsmc_ssm_stmt& s = q < sp->n_init ? sp->init[q] : sp->step[q - sp->n_init];
-        if (s.kind == WSMC_SSM_ASSIGN_EXPR) nprog += s.prog_len;
-        if (s.kind == WSMC_SSM_SAMPLE || s.kind == WSMC_SSM_OBSERVE) feat |= wsmc_dist_feat(&s.dist);
-    }
-    // the persistent workgroup: one unsharded context, N within the cap for S columns, a stratified
-    // / systematic scheme, no column but the spec's, the weights unchanged (so a Resample after a
-    // SAMPLE never runs), and the programs within the kernel's arguments
-    bool persistent = !c->multi && !is_sharded(c) && c->N <= ssm_cap(S) && scheme != WSMC_RESAMPLE_MULTINOMIAL &&
-                      !c->weights_changed && nprog <= kSsmProgMax;
-    std::string foreign;
-    if (persistent)
-        for (const auto& col : c->cols) {
-            bool in = false;
-            for (int k = 0; k < S; ++k) in |= col.name == sp->col_names[k];
-            persistent &= in;
-            if (!in && foreign.empty()) foreign = col.name;
-        }
+    const SsmShape sh = ssm_shape(sp);
+    const unsigned feat = sh.feat;
+    const std::string why = ssm_route_why(c, sp, sh, c->N, scheme, true);
+    const bool persistent = why.empty();   // else the statements: any handle, any N, any scheme
     // a smoothed run has the persistent route only (the store could not drop the T n_cols columns
     // the statements would leave): refused here, before anything of the context changes
     const bool smooth = sm.paths || sm.mean || sm.var;
-    const int n_obs = ssm_count_observes(sp);
+    if (smooth && !persistent) return fail(WSMC_EARG, "ssm smoothed run: " + why);
     SsmSlab sm_slab;
     SsmSmoothClock sm_clock;
     size_t sm_bytes = 0;
     SsmSmoothBufs sb;
     std::memset(&sb, 0, sizeof(sb));
     if (smooth) {
-        const std::string who = "ssm smoothed run: ";
-        if (c->multi || is_sharded(c)) return fail(WSMC_EARG, who + "a sharded or multi-device context (one unsharded device runs it)");
-        if (c->N > ssm_cap(S))
-            return fail(WSMC_EARG, who + "n = " + std::to_string(c->N) + " above the cap of " + std::to_string(ssm_cap(S)) +
-                                       " particles for " + std::to_string(S) + " columns");
-        if (scheme == WSMC_RESAMPLE_MULTINOMIAL)
-            return fail(WSMC_EARG, who + "multinomial resampling (the persistent workgroup has stratified and systematic)");
-        if (c->weights_changed) return fail(WSMC_EARG, who + "weights_changed is set (a Resample after a SAMPLE could run)");
-        if (nprog > kSsmProgMax)
-            return fail(WSMC_EARG, who + std::to_string(nprog) + " program instructions (more than " + std::to_string(kSsmProgMax) + ")");
-        if (!persistent) return fail(WSMC_EARG, who + "the context holds a column that is not the spec's (" + foreign + ")");
         WSMC_HIP(hipSetDevice(c->device));
-        const size_t bytes = sm_bytes = ssm_smooth_carve(nullptr, sm, 1, T, c->N, S, n_obs, nullptr);
+        const size_t bytes = sm_bytes = ssm_smooth_carve(nullptr, sm, 1, T, c->N, S, sh.n_obs, nullptr);
         if (int rc = ssm_smooth_alloc(&sm_slab, bytes + 256, "ssm smoothed run")) return rc;
         WSMC_HIP(sm_clock.start());
-        ssm_smooth_carve(sm_slab.p, sm, 1, T, c->N, S, n_obs, &sb);
+        ssm_smooth_carve(sm_slab.p, sm, 1, T, c->N, S, sh.n_obs, &sb);
     }
     for (int k = 0; k < S; ++k)   // the missing ones, in order
         if (int rc = wsmc_col_create(c, sp->col_names[k], 1, &ids[k])) return rc;
     if (!persistent) {
-        int rc = ssm_statements(c, sp, ids, data, T, ess_min, scheme, tr);
+        int rc = ssm_statements(c, sp, sh, ids, data, T, ess_min, scheme, tr);
         if (rc) return rc;
         sc->ssm_stmt_runs += 1;
         sc->ssm_book_us = 0;
@@ -5766,41 +5816,16 @@ static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int
         sc->ssm_wall_us = us(t_in, clk::now());
         return WSMC_OK;
     }
-    CHECK_CTX(c);   // an asynchronous run, the open statement batch, unstored Samples, a pending reset
-    if (int rc = resolve_decisions(c)) return rc;
-    if (int rc = check_deferred(c)) return rc;
-    scores_invalidate(c);   // the run rewrites the columns the tape reads
-    if (int rc = materialize(c, nullptr)) return rc;   // `init` may read a column a lazy Resample left behind
-    c->wseq += 1;           // ... and the weights
+    if (int rc = persistent_enter(c, true)) return rc;   // (stored: `init` may read a column)
     const int dd = sp->data_dim;
     const int64_t ndata = (int64_t)T * dd;
-    if (c->lg_data_cap < ndata) {
-        WSMC_HIP(ctx_sync(c, c->stream));
-        if (c->lg_data) WSMC_HIP(hipFree(c->lg_data));
-        c->lg_data = nullptr;
-        c->lg_data_cap = 0;
-        WSMC_HIP(hipMalloc(&c->lg_data, sizeof(double) * (size_t)ndata));
-        c->lg_data_cap = ndata;
-    }
-    if (ess_trace_out && c->lg_trace_cap < T) {
-        WSMC_HIP(ctx_sync(c, c->stream));
-        if (c->lg_trace) WSMC_HIP(hipFree(c->lg_trace));
-        c->lg_trace = nullptr;
-        c->lg_trace_cap = 0;
-        WSMC_HIP(hipMalloc(&c->lg_trace, sizeof(double) * (size_t)T));
-        c->lg_trace_cap = T;
-    }
+    if (int rc = ctx_grow(c, &c->lg_data, &c->lg_data_cap, ndata)) return rc;
+    if (ess_trace_out)
+        if (int rc = ctx_grow(c, &c->lg_trace, &c->lg_trace_cap, T)) return rc;
     if (!c->lg_rec) WSMC_HIP(hipMalloc(&c->lg_rec, sizeof(LgRecord)));
     // the trace's rows: a buffer of the context, as the ESS trace's is, grown to what was asked
     const size_t n_mean = tr.mean ? (size_t)T * S : 0, n_var = tr.var ? (size_t)T * S : 0, n_le = tr.log_evidence ? (size_t)T : 0;
-    if ((int64_t)(n_mean + n_var + n_le) > c->ssm_rows_cap) {
-        WSMC_HIP(ctx_sync(c, c->stream));
-        if (c->ssm_rows) WSMC_HIP(hipFree(c->ssm_rows));
-        c->ssm_rows = nullptr;
-        c->ssm_rows_cap = 0;
-        WSMC_HIP(hipMalloc(&c->ssm_rows, sizeof(double) * (n_mean + n_var + n_le)));
-        c->ssm_rows_cap = (int64_t)(n_mean + n_var + n_le);
-    }
+    if (int rc = ctx_grow(c, &c->ssm_rows, &c->ssm_rows_cap, (int64_t)(n_mean + n_var + n_le))) return rc;
     if (ndata > 0)
         WSMC_HIP(hipMemcpyAsync(c->lg_data, data, sizeof(double) * (size_t)ndata, hipMemcpyHostToDevice, c->stream));
     WSMC_HIP(hipMemsetAsync(c->lg_rec, 0, sizeof(LgRecord), c->stream));
@@ -5818,32 +5843,17 @@ static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int
     ka.data = c->lg_data;
     ka.ess_trace = ess_trace_out ? c->lg_trace : nullptr;
     ka.rec = c->lg_rec;
-    ka.N = (int32_t)c->N;
     const int threads = ssm_threads(feat, (int)c->N);
-    ka.P = (int32_t)((c->N + threads - 1) / threads);
-    ka.S = S;
-    ka.data_dim = dd;
-    ka.scheme = scheme;
-    ka.n_init = sp->n_init;
-    ka.n_step = sp->n_step;
-    ka.init_ops = ssm_op_count(sp->init, sp->n_init);
-    ka.step_ops = ssm_op_count(sp->step, sp->n_step);
-    ka.last_obs = ssm_last_observe(sp);
+    ssm_fill_args(ka, sh, c->N, threads, scheme, ess_min);
     ka.seed = c->seed;
     ka.op_base = c->op;
-    ka.ess_min = ess_min;
-    int nins = 0;
-    for (int q = 0; q < sp->n_init; ++q) ka.init[q] = ssm_dev_stmt(sp->init[q], ka.ins, &nins);
-    for (int q = 0; q < sp->n_step; ++q) ka.step[q] = ssm_dev_stmt(sp->step[q], ka.ins, &nins);
+    ssm_dev_image(sp, ka.init, ka.step, ka.ins);
     // every segment back to back on the stream; the state between them is the columns, w, anc and rec
-    const int32_t K = c->ssm_segment > 0 ? c->ssm_segment
-                                         : std::max(1, kSsmSegmentStmts / sp->n_step * 2 / std::max(2, (int)ka.P));
+    const int32_t K = c->ssm_segment > 0 ? c->ssm_segment : ssm_default_steps(sh, ka.P);
     int64_t nseg = 0;
     WSMC_HIP(sm_clock.mark(0, c->stream));
     for (int32_t t0 = 0; t0 < T; t0 += K, ++nseg) {
-        ka.t0 = t0;
-        ka.nsteps = std::min<int32_t>(K, T - t0);
-        ka.first = t0 == 0;
+        set_segment(ka, t0, K, T);
         if (smooth)
             WSMC_HIP(launch_ssm_segment_rec(c->stream, kra, feat, threads));
         else
@@ -5873,10 +5883,7 @@ static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int
     const auto t_book = clk::now();
     for (int k = 0; k < S; ++k) wrote_col(c, ids[k]);
     gc_log(c);
-    int nterm_init = 0, nterm_step = 0;
-    for (int q = 0; q < sp->n_init; ++q) nterm_init += sp->init[q].kind == WSMC_SSM_SAMPLE || sp->init[q].kind == WSMC_SSM_OBSERVE;
-    for (int q = 0; q < sp->n_step; ++q) nterm_step += sp->step[q].kind == WSMC_SSM_SAMPLE || sp->step[q].kind == WSMC_SSM_OBSERVE;
-    c->tape.reserve(c->tape.size() + (size_t)nterm_init + (size_t)nterm_step * (size_t)T);
+    c->tape.reserve(c->tape.size() + (size_t)sh.init_terms + (size_t)sh.step_terms * (size_t)T);
     auto book = [&](const wsmc_ssm_stmt& s, const double* row) {
         if (s.kind == WSMC_SSM_SAMPLE) {
             push_sample_term(c, ids[s.col], ssm_map_dist(s.dist, ids, row));
@@ -5901,11 +5908,7 @@ static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int
     const auto t_booked = clk::now();
     WSMC_HIP(ctx_sync(c, c->stream));
     if (smooth) sm_clock.read(c, sm_bytes);
-    c->resampled = hrec.last_dec;
-    c->last_ess = hrec.last_ess;
-    c->n_resamples += hrec.nres;
-    if (hrec.nres) set_anc_last(c, nullptr, -1);   // the last resampling step's row is in c->anc
-    c->wseq += 1;
+    persistent_leave(c, hrec);
     c->ssm_runs += 1;
     c->ssm_segments += nseg;
     c->ssm_book_us = us(t_book, t_booked);
@@ -5918,22 +5921,17 @@ static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int
 int wsmc_ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int32_t T, double ess_min, int32_t scheme,
                  double* log_evidence_out, double* ess_trace_out) {
     const wsmc_ssm_trace tr = {ess_trace_out, nullptr, nullptr, nullptr};
-    const wsmc_ssm_smooth no_smooth = {nullptr, nullptr, nullptr};
-    return ssm_run(c, sp, data, T, ess_min, scheme, log_evidence_out, tr, no_smooth);
+    return ssm_run(c, sp, data, T, ess_min, scheme, log_evidence_out, tr, kNoSmooth);
 }
 
 int wsmc_ssm_run_traced(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int32_t T, double ess_min, int32_t scheme,
                         double* log_evidence_out, const wsmc_ssm_trace* trace) {
-    const wsmc_ssm_trace none = {nullptr, nullptr, nullptr, nullptr};
-    const wsmc_ssm_smooth no_smooth = {nullptr, nullptr, nullptr};
-    return ssm_run(c, sp, data, T, ess_min, scheme, log_evidence_out, trace ? *trace : none, no_smooth);
+    return ssm_run(c, sp, data, T, ess_min, scheme, log_evidence_out, trace ? *trace : kNoTrace, kNoSmooth);
 }
 
 int wsmc_ssm_run_smoothed(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int32_t T, double ess_min, int32_t scheme,
                           double* log_evidence_out, const wsmc_ssm_trace* trace, const wsmc_ssm_smooth* smooth) {
-    const wsmc_ssm_trace none = {nullptr, nullptr, nullptr, nullptr};
-    const wsmc_ssm_smooth no_smooth = {nullptr, nullptr, nullptr};
-    return ssm_run(c, sp, data, T, ess_min, scheme, log_evidence_out, trace ? *trace : none, smooth ? *smooth : no_smooth);
+    return ssm_run(c, sp, data, T, ess_min, scheme, log_evidence_out, trace ? *trace : kNoTrace, smooth ? *smooth : kNoSmooth);
 }
 
 int wsmc_debug_ssm(wsmc_ctx* c, int32_t segment_steps, int64_t* stats_out) {
@@ -6022,13 +6020,13 @@ int wsmc_ssm_batch_out_sizeof(int64_t* bytes) {
     return WSMC_OK;
 }
 
-// wsmc_ssm_run_batch and wsmc_ssm_run_batch_traced: tr's members are null where nothing is wanted
+// wsmc_ssm_run_batch, wsmc_ssm_run_batch_traced and wsmc_ssm_run_batch_smoothed: tr's and sm's
+// members are null where nothing is wanted
 static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_specs, const double* data, int32_t n_tables,
                          int32_t T, int32_t n, int32_t B, const uint64_t* seeds, double ess_min, int32_t scheme,
                          wsmc_ssm_batch_out* out, const wsmc_ssm_trace& tr, const wsmc_ssm_smooth& sm) {
     // every refusal before any device call; the context's state is never read past its layout
     if (!c) return fail(WSMC_EARG, "null context");
-    if (c->multi || is_sharded(c)) return fail(WSMC_EARG, "ssm batch: a sharded or multi-device context (one unsharded device runs a batch)");
     if (B < 1) return fail(WSMC_EARG, "ssm batch: B < 1");
     if (T < 1) return fail(WSMC_EARG, "ssm batch: T < 1");
     if (n < 1) return fail(WSMC_EARG, "ssm batch: n < 1");
@@ -6047,37 +6045,22 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
     const int S = sp->n_cols, dd = sp->data_dim;
     if (dd > 0 && !data) return fail(WSMC_EARG, "ssm batch: null data for a spec that reads data");
     if (!valid_scheme(scheme)) return fail(WSMC_EARG, "ssm batch: unknown resampling scheme");
-    if (scheme == WSMC_RESAMPLE_MULTINOMIAL)
-        return fail(WSMC_EARG, "ssm batch: multinomial resampling (the persistent workgroup has stratified and systematic)");
-    if (n > ssm_cap(S))
-        return fail(WSMC_EARG, "ssm batch: n = " + std::to_string(n) + " above the cap of " + std::to_string(ssm_cap(S)) + " particles for " +
-                                   std::to_string(S) + " columns");
-    int nprog = 0;
-    unsigned feat = 0;
-    for (int q = 0; q < sp->n_init + sp->n_step; ++q) {
-        const wsmc_ssm_stmt& s = q < sp->n_init ? sp->init[q] : sp->step[q - sp->n_init];
-        if (s.kind == WSMC_SSM_ASSIGN_EXPR) nprog += s.prog_len;
-        if (s.kind == WSMC_SSM_SAMPLE || s.kind == WSMC_SSM_OBSERVE) feat |= wsmc_dist_feat(&s.dist);
-    }
-    if (nprog > kSsmProgMax)
-        return fail(WSMC_EARG, "ssm batch: " + std::to_string(nprog) + " program instructions (more than " + std::to_string(kSsmProgMax) + ")");
-    using clk = std::chrono::steady_clock;
+    const SsmShape sh = ssm_shape(sp);   // (the filters' particles are the call's own: no state of the context decides)
+    const unsigned feat = sh.feat;
+    const std::string why = ssm_route_why(c, sp, sh, n, scheme, false);
+    if (!why.empty()) return fail(WSMC_EARG, "ssm batch: " + why);
     const auto t_in = clk::now();
     WSMC_HIP(hipSetDevice(c->device));
 
-    // the images: ssm_dev_stmt per spec, so a filter's parameter bits are the single run's
+    // the images, per spec
     std::vector<SsmBatchFilter> filt((size_t)B);
     std::memset(filt.data(), 0, sizeof(SsmBatchFilter) * (size_t)B);
     for (int32_t b = 0; b < B; ++b) {
-        const wsmc_ssm_spec* sb = specs + (n_specs == 1 ? 0 : b);
         SsmBatchFilter& f = filt[(size_t)b];
-        if (b > 0 && n_specs == 1) {
+        if (b > 0 && n_specs == 1)
             f = filt[0];
-        } else {
-            int nins = 0;
-            for (int q = 0; q < sb->n_init; ++q) f.init[q] = ssm_dev_stmt(sb->init[q], f.ins, &nins);
-            for (int q = 0; q < sb->n_step; ++q) f.step[q] = ssm_dev_stmt(sb->step[q], f.ins, &nins);
-        }
+        else
+            ssm_dev_image(specs + b, f.init, f.step, f.ins);
         f.seed = seeds[b];
     }
     // one allocation for the call: the state between segments ([B] rows of what a context keeps:
@@ -6092,7 +6075,7 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
                  nle = tr.log_evidence ? up(sizeof(double) * (size_t)B * T) : 0;
     const size_t nstate = nx + nw + nanc + nrec;
     const bool smooth = sm.paths || sm.mean || sm.var;
-    const int n_obs = ssm_count_observes(sp);
+    const int n_obs = sh.n_obs;
     const size_t nsmooth = smooth ? ssm_smooth_carve(nullptr, sm, B, T, n, S, n_obs, nullptr) : 0;
     SsmSlab slab;
     SsmSmoothClock sm_clock;
@@ -6146,20 +6129,10 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
     ka.tr_logev = d_le;
     ka.rec = d_rec;
     ka.filt = d_filt;
-    ka.N = n;
     const int threads = ssm_threads(feat, n);
-    ka.P = (n + threads - 1) / threads;
-    ka.S = S;
-    ka.data_dim = dd;
-    ka.scheme = scheme;
-    ka.n_init = sp->n_init;
-    ka.n_step = sp->n_step;
-    ka.init_ops = ssm_op_count(sp->init, sp->n_init);
-    ka.step_ops = ssm_op_count(sp->step, sp->n_step);
-    ka.last_obs = ssm_last_observe(sp);
+    ssm_fill_args(ka, sh, n, threads, scheme, ess_min);
     ka.T = T;
     ka.B = B;
-    ka.ess_min = ess_min;
     // steps a launch: the single run's, divided by the rounds of resident workgroups the batch
     // takes, so a launch stays near the single run's 25 ms whatever B is
     int per_cu = 0, cus = 0;
@@ -6169,13 +6142,11 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
     if (e == hipSuccess) {
         const int64_t resident = (int64_t)per_cu * cus;
         const int64_t rounds = ((int64_t)B + resident - 1) / resident;
-        const int32_t K1 = std::max(1, kSsmSegmentStmts / sp->n_step * 2 / std::max(2, (int)ka.P));
-        const int32_t K = c->ssm_batch_segment > 0 ? c->ssm_batch_segment : (int32_t)std::max<int64_t>(1, K1 / rounds);
+        const int32_t K = c->ssm_batch_segment > 0 ? c->ssm_batch_segment
+                                                   : (int32_t)std::max<int64_t>(1, ssm_default_steps(sh, ka.P) / rounds);
         e = sm_clock.mark(0, st);
         for (int32_t t0 = 0; t0 < T && e == hipSuccess; t0 += K, ++nseg) {
-            ka.t0 = t0;
-            ka.nsteps = std::min<int32_t>(K, T - t0);
-            ka.first = t0 == 0;
+            set_segment(ka, t0, K, T);
             ka.last = t0 + ka.nsteps == T;
             e = smooth ? launch_ssm_batch_segment_rec(st, kra, feat, threads) : launch_ssm_batch_segment(st, ka, feat, threads);
         }
@@ -6225,33 +6196,27 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
     c->ssm_batch_per_cu = per_cu;
     c->ssm_batch_cus = cus;
     c->ssm_batch_segments = nseg;
-    c->ssm_batch_wall_us = (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(clk::now() - t_in).count();
+    c->ssm_batch_wall_us = us(t_in, clk::now());
     return WSMC_OK;
 }
 
 int wsmc_ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_specs, const double* data, int32_t n_tables,
                        int32_t T, int32_t n, int32_t B, const uint64_t* seeds, double ess_min, int32_t scheme,
                        wsmc_ssm_batch_out* out) {
-    const wsmc_ssm_trace none = {nullptr, nullptr, nullptr, nullptr};
-    const wsmc_ssm_smooth no_smooth = {nullptr, nullptr, nullptr};
-    return ssm_run_batch(c, specs, n_specs, data, n_tables, T, n, B, seeds, ess_min, scheme, out, none, no_smooth);
+    return ssm_run_batch(c, specs, n_specs, data, n_tables, T, n, B, seeds, ess_min, scheme, out, kNoTrace, kNoSmooth);
 }
 
 int wsmc_ssm_run_batch_traced(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_specs, const double* data, int32_t n_tables,
                               int32_t T, int32_t n, int32_t B, const uint64_t* seeds, double ess_min, int32_t scheme,
                               wsmc_ssm_batch_out* out, const wsmc_ssm_trace* trace) {
-    const wsmc_ssm_trace none = {nullptr, nullptr, nullptr, nullptr};
-    const wsmc_ssm_smooth no_smooth = {nullptr, nullptr, nullptr};
-    return ssm_run_batch(c, specs, n_specs, data, n_tables, T, n, B, seeds, ess_min, scheme, out, trace ? *trace : none, no_smooth);
+    return ssm_run_batch(c, specs, n_specs, data, n_tables, T, n, B, seeds, ess_min, scheme, out, trace ? *trace : kNoTrace, kNoSmooth);
 }
 
 int wsmc_ssm_run_batch_smoothed(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_specs, const double* data, int32_t n_tables,
                                 int32_t T, int32_t n, int32_t B, const uint64_t* seeds, double ess_min, int32_t scheme,
                                 wsmc_ssm_batch_out* out, const wsmc_ssm_trace* trace, const wsmc_ssm_smooth* smooth) {
-    const wsmc_ssm_trace none = {nullptr, nullptr, nullptr, nullptr};
-    const wsmc_ssm_smooth no_smooth = {nullptr, nullptr, nullptr};
-    return ssm_run_batch(c, specs, n_specs, data, n_tables, T, n, B, seeds, ess_min, scheme, out, trace ? *trace : none,
-                         smooth ? *smooth : no_smooth);
+    return ssm_run_batch(c, specs, n_specs, data, n_tables, T, n, B, seeds, ess_min, scheme, out, trace ? *trace : kNoTrace,
+                         smooth ? *smooth : kNoSmooth);
 }
 
 int wsmc_debug_ssm_smooth(wsmc_ctx* c, int64_t* stats_out) {

@@ -169,11 +169,7 @@ __global__ __launch_bounds__(THREADS) void WSMC_SSM_KERNEL(SsKernArgs) {
 
 template <unsigned FEAT, int THREADS>
 static hipError_t ssm_launch(hipStream_t s, const SsKernArgs& a, int threads, size_t lds) {
-    if (lds > 65536 - 4096) {   // past 64 KiB a kernel must ask for its dynamic LDS (per device: set at each launch)
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(WSMC_SSM_KERNEL<FEAT, THREADS, kSsTraced>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (const hipError_t e = ss_ask_lds(WSMC_SSM_KERNEL<FEAT, THREADS, kSsTraced>, lds); e != hipSuccess) return e;
     hipLaunchKernelGGL((WSMC_SSM_KERNEL<FEAT, THREADS, kSsTraced>), dim3(1), dim3(threads), lds, s, a);
     return hipGetLastError();
 }
@@ -195,24 +191,15 @@ hipError_t ssm_launch_traced(hipStream_t s, const SsmArgs& a, unsigned feat, int
 
 hipError_t ssm_launch_rec(hipStream_t s, const SsmRecArgs& a, unsigned feat, int threads, size_t lds);   // csrc/wsmc_ssm_smooth.hip
 
-static bool ssm_segment_ok(const SsmArgs& a, unsigned feat, int threads) {
-    const int tmax = (feat & WSMC_FEAT_GAM) ? kSsGamThreads : kSsMaxThreads;
-    return !(a.S < 1 || a.S > WSMC_SSM_MAX_COLS || a.N < 1 || a.N > ssm_cap(a.S) || threads < 64 || threads > tmax ||
-        (threads & 63) || (int64_t)a.P * threads < a.N || a.nsteps < 0 || a.t0 < 0 || a.data_dim < 0 ||
-        a.data_dim > WSMC_SSM_MAX_DATA || a.n_init < 0 || a.n_init > WSMC_SSM_MAX_INIT || a.n_step < 1 ||
-        a.n_step > WSMC_SSM_MAX_STMTS) &&
-           ssm_lds_bytes(a.N, a.S) + 4096 <= 160 * 1024;   // with the static tables: the workgroup's LDS
-}
-
 hipError_t launch_ssm_segment(hipStream_t s, const SsmArgs& a, unsigned feat, int threads) {
-    if (!ssm_segment_ok(a, feat, threads)) return hipErrorInvalidValue;
+    if (!ss_segment_ok(a, feat, threads)) return hipErrorInvalidValue;
     const size_t lds = ssm_lds_bytes(a.N, a.S);
     if (a.tr_mean || a.tr_var || a.tr_logev) return ssm_launch_traced(s, a, feat, threads, lds);
     return ssm_launch_untraced(s, a, feat, threads, lds);
 }
 
 hipError_t launch_ssm_segment_rec(hipStream_t s, const SsmRecArgs& a, unsigned feat, int threads) {
-    if (!ssm_segment_ok(a.a, feat, threads) || !a.r.hist || !a.r.alog || !a.r.ran || a.r.n_obs < 1 ||
+    if (!ss_segment_ok(a.a, feat, threads) || !a.r.hist || !a.r.alog || !a.r.ran || a.r.n_obs < 1 ||
         a.a.t0 + a.a.nsteps > a.r.T)
         return hipErrorInvalidValue;
     return ssm_launch_rec(s, a, feat, threads, ssm_lds_bytes(a.a.N, a.a.S));

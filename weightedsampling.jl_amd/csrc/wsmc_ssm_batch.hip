@@ -223,20 +223,13 @@ namespace {
 template <unsigned FEAT, int THREADS>
 hipError_t ssb_occupancy(int threads, size_t lds, int* per_cu) {
     const void* k = reinterpret_cast<const void*>(WSMC_SSB_KERNEL<FEAT, THREADS, kSsbTraced>);
-    if (lds > 65536 - 4096) {   // the occupancy query refuses dynamic LDS the kernel has not asked for
-        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (const hipError_t e = ss_ask_lds(k, lds); e != hipSuccess) return e;
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k, threads, lds);
 }
 
 template <unsigned FEAT, int THREADS>
 hipError_t ssb_launch(hipStream_t s, const SsbKernArgs& a, int threads, size_t lds, int B) {
-    if (lds > 65536 - 4096) {   // past 64 KiB a kernel must ask for its dynamic LDS (per device: set at each launch)
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(WSMC_SSB_KERNEL<FEAT, THREADS, kSsbTraced>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (const hipError_t e = ss_ask_lds(WSMC_SSB_KERNEL<FEAT, THREADS, kSsbTraced>, lds); e != hipSuccess) return e;
     hipLaunchKernelGGL((WSMC_SSB_KERNEL<FEAT, THREADS, kSsbTraced>), dim3((unsigned)B), dim3(threads), lds, s, a);
     return hipGetLastError();
 }
@@ -269,12 +262,7 @@ hipError_t ssm_batch_occupancy(int device, unsigned feat, int variant, int threa
 }
 
 static bool ssb_segment_ok(const SsmBatchArgs& a, unsigned feat, int threads) {
-    const int tmax = (feat & WSMC_FEAT_GAM) ? kSsGamThreads : kSsMaxThreads;
-    return !(a.B < 1 || a.S < 1 || a.S > WSMC_SSM_MAX_COLS || a.N < 1 || a.N > ssm_cap(a.S) || threads < 64 || threads > tmax ||
-        (threads & 63) || (int64_t)a.P * threads < a.N || a.nsteps < 0 || a.t0 < 0 || a.t0 + a.nsteps > a.T ||
-        a.data_dim < 0 || a.data_dim > WSMC_SSM_MAX_DATA || a.n_init < 0 || a.n_init > WSMC_SSM_MAX_INIT || a.n_step < 1 ||
-        a.n_step > WSMC_SSM_MAX_STMTS || !a.x || !a.w || !a.anc || !a.rec || !a.filt) &&
-           ssm_lds_bytes(a.N, a.S) + 4096 <= 160 * 1024;   // with the static tables: the workgroup's LDS
+    return ss_segment_ok(a, feat, threads) && a.B >= 1 && a.t0 + a.nsteps <= a.T && a.x && a.w && a.anc && a.rec && a.filt;
 }
 
 hipError_t launch_ssm_batch_segment(hipStream_t s, const SsmBatchArgs& a, unsigned feat, int threads) {

@@ -483,6 +483,25 @@ __device__ inline void ss_record_anc(const SsState& L, int32_t* slot, int32_t* r
 constexpr unsigned kSsFeatExt = WSMC_FEAT_EXT, kSsFeatGam = WSMC_FEAT_EXT | WSMC_FEAT_GAM;
 constexpr int kSsGamThreads = 1024;
 
+// ---- host side: what the launch wrappers of both files share (no kernel calls these) ----
+// a segment's arguments within the kernels' limits, for the fields SsmArgs and SsmBatchArgs share
+template <class Args>
+inline bool ss_segment_ok(const Args& a, unsigned feat, int threads) {
+    const int tmax = (feat & WSMC_FEAT_GAM) ? kSsGamThreads : kSsMaxThreads;
+    return !(a.S < 1 || a.S > WSMC_SSM_MAX_COLS || a.N < 1 || a.N > ssm_cap(a.S) || threads < 64 || threads > tmax ||
+        (threads & 63) || (int64_t)a.P * threads < a.N || a.nsteps < 0 || a.t0 < 0 || a.data_dim < 0 ||
+        a.data_dim > WSMC_SSM_MAX_DATA || a.n_init < 0 || a.n_init > WSMC_SSM_MAX_INIT || a.n_step < 1 ||
+        a.n_step > WSMC_SSM_MAX_STMTS) &&
+           ssm_lds_bytes(a.N, a.S) + 4096 <= 160 * 1024;   // with the static tables: the workgroup's LDS
+}
+// past 64 KiB a kernel must ask for its dynamic LDS (per device: set at each launch, and before an
+// occupancy query, which refuses what the kernel has not asked for)
+template <class Kernel>
+inline hipError_t ss_ask_lds(Kernel k, size_t lds) {
+    if (lds <= 65536 - 4096) return hipSuccess;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+
 }  // namespace
 
 }  // namespace wsmc

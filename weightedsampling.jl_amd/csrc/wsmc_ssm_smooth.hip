@@ -142,11 +142,7 @@ hipError_t launch_ssm_smooth_rows(hipStream_t s, const SsmRec& r, const double* 
     // the fused kernel's layout without the ancestors: S + 1 column buffers, the log-weights, the scratch
     const size_t lds = ((size_t)S + 2) * ss_n8(N) * sizeof(double) + kSsScratch * sizeof(uint64_t);
     if (lds + 4096 > 160 * 1024) return hipErrorInvalidValue;
-    if (lds > 65536 - 4096) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ssm_smooth_rows),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (const hipError_t e = ss_ask_lds(k_ssm_smooth_rows, lds); e != hipSuccess) return e;
     SsmRowsArgs a;
     a.r = r;
     a.w = w;

@@ -15,7 +15,8 @@ import numpy as np
 
 from . import abi
 from .abi import Dist, Operand, RunTiming, State, check, load_library
-from .ssm import SsmSmooth, SsmTrace, batch_arguments, smooth_parts
+from .ssm import (TRACE_PARTS, SsmSmooth, SsmTrace, batch_arguments, smooth_buffers, smooth_by_name, smooth_parts, trace_buffers,
+                  trace_by_name, trace_parts)
 
 _D = C.POINTER(C.c_double)
 _I32P = C.POINTER(C.c_int32)
@@ -501,35 +502,17 @@ class Context:
         if trace or sparts:
             if ess_trace:
                 raise ValueError("ess_trace and trace: the trace holds the ESS% (SsmTrace.ess)")
-            parts = ("ess", "mean", "var", "log_evidence") if trace is True else tuple(trace or ())
-            bad = [p for p in parts if p not in ("ess", "mean", "var", "log_evidence")]
-            if bad:
-                raise ValueError(f"trace: unknown part {bad[0]!r}")
             steps, S = len(tab), len(spec.cols)
-            buf = {"ess": np.empty(steps), "mean": np.empty((steps, S)), "var": np.empty((steps, S)),
-                   "log_evidence": np.empty(steps)}
-            out = abi.SsmTraceOut()
-            for p in parts:
-                setattr(out, p, _dptr(buf[p]))
-            by_name = lambda a: {c: a[:, k].copy() for k, c in enumerate(spec.cols)}
+            buf, out = trace_buffers(trace_parts(trace), (steps,), S)
             head = (self._h, C.byref(spec.spec), _dptr(tab) if tab.size else None, steps, float(ess_perc_min), int(scheme),
                     C.byref(ev) if want_evidence else None, C.byref(out))
             if sparts:
-                sbuf = {"paths": np.empty((steps, S, self.n)) if "paths" in sparts else None,
-                        "mean": np.empty((steps, S)) if "mean" in sparts else None,
-                        "var": np.empty((steps, S)) if "var" in sparts else None}
-                so = abi.SsmSmoothOut()
-                for p in sparts:
-                    setattr(so, p, _dptr(sbuf[p]))
+                sbuf, so = smooth_buffers(sparts, (steps,), S, self.n)
                 check(self._L.wsmc_ssm_run_smoothed(*head, C.byref(so)))
-                sm = SsmSmooth({c: sbuf["paths"][:, k, :] for k, c in enumerate(spec.cols)} if "paths" in sparts else None,
-                               by_name(sbuf["mean"]) if "mean" in sparts else None,
-                               by_name(sbuf["var"]) if "var" in sparts else None, self.weights_download())
+                sm = SsmSmooth(*smooth_by_name(sbuf, spec.cols), self.weights_download())
             else:
                 check(self._L.wsmc_ssm_run_traced(*head))
-            tr = SsmTrace(buf["ess"] if "ess" in parts else None, by_name(buf["mean"]) if "mean" in parts else None,
-                          by_name(buf["var"]) if "var" in parts else None,
-                          buf["log_evidence"] if "log_evidence" in parts else None)
+            tr = SsmTrace(*trace_by_name(buf, spec.cols))
             res = ((float(ev.value) if want_evidence else None),) + ((tr,) if trace else ()) + ((sm,) if sparts else ())
             return res
         tr = np.empty(len(tab)) if ess_trace else None
@@ -587,8 +570,9 @@ class Context:
         out.log_evidence = _dptr(res.log_evidence)
         out.n_resamples = res.n_resamples.ctypes.data_as(C.POINTER(C.c_int64))
         out.last_resampled = res.last_resampled.ctypes.data_as(_I32P)
-        if ess_trace:
-            res.ess = np.empty((B, steps))
+        tbuf, tr = trace_buffers(TRACE_PARTS if trace else (), (B, steps), S)
+        if ess_trace:   # (with the trace as well: one buffer for both)
+            res.ess = tbuf["ess"] if trace else np.empty((B, steps))
             out.ess_trace = _dptr(res.ess)
         if state:
             cols = np.empty((B, S, int(n)))
@@ -599,35 +583,16 @@ class Context:
             out.last_ancestors = res.last_ancestors.ctypes.data_as(_I32P)
         args = (self._h, arr, len(spec_list), _dptr(tab) if tab is not None else None, len(tabs), steps, int(n), B,
                 seeds_a.ctypes.data_as(C.POINTER(C.c_uint64)), float(ess_perc_min), int(scheme), C.byref(out))
-        tr = abi.SsmTraceOut()
-        if trace:
-            mean, var = np.empty((B, steps, S)), np.empty((B, steps, S))
-            res.log_evidence_trace = np.empty((B, steps))
-            if res.ess is None:
-                res.ess = np.empty((B, steps))
-            tr.ess, tr.mean, tr.var = _dptr(res.ess), _dptr(mean), _dptr(var)
-            tr.log_evidence = _dptr(res.log_evidence_trace)
         if sparts:
-            so = abi.SsmSmoothOut()
-            sbuf = {"paths": np.empty((B, steps, S, int(n))) if "paths" in sparts else None,
-                    "mean": np.empty((B, steps, S)) if "mean" in sparts else None,
-                    "var": np.empty((B, steps, S)) if "var" in sparts else None}
-            for p in sparts:
-                setattr(so, p, _dptr(sbuf[p]))
+            sbuf, so = smooth_buffers(sparts, (B, steps), S, int(n))
             check(self._L.wsmc_ssm_run_batch_smoothed(*args, C.byref(tr), C.byref(so)))
-            if "paths" in sparts:
-                res.paths = {name: sbuf["paths"][:, :, k, :] for k, name in enumerate(first.cols)}
-            if "mean" in sparts:
-                res.smean = {name: sbuf["mean"][:, :, k].copy() for k, name in enumerate(first.cols)}
-            if "var" in sparts:
-                res.svar = {name: sbuf["var"][:, :, k].copy() for k, name in enumerate(first.cols)}
+            res.paths, res.smean, res.svar = smooth_by_name(sbuf, first.cols)
         elif trace:
             check(self._L.wsmc_ssm_run_batch_traced(*args, C.byref(tr)))
         else:
             check(self._L.wsmc_ssm_run_batch(*args))
         if trace:
-            res.mean = {name: mean[:, :, k].copy() for k, name in enumerate(first.cols)}
-            res.var = {name: var[:, :, k].copy() for k, name in enumerate(first.cols)}
+            res.ess, res.mean, res.var, res.log_evidence_trace = trace_by_name(tbuf, first.cols)
         res.last_resampled = res.last_resampled.astype(bool)
         if state:
             res.cols = {name: cols[:, k, :] for k, name in enumerate(first.cols)}

@@ -88,6 +88,52 @@ def smooth_parts(smooth) -> tuple:
     return parts
 
 
+TRACE_PARTS = ("ess", "mean", "var", "log_evidence")
+
+
+def trace_parts(trace) -> tuple:
+    """Context.ssm_run's `trace` argument as the parts wanted: () for a false value, all four for
+    True, else the names given (ValueError for one that is none of them)"""
+    parts = TRACE_PARTS if trace is True else tuple(trace or ())
+    bad = [p for p in parts if p not in TRACE_PARTS]
+    if bad:
+        raise ValueError(f"trace: unknown part {bad[0]!r}")
+    return parts
+
+
+def _out_buffers(out, shapes: dict):
+    """a host array per part wanted, and `out` (SsmTraceOut / SsmSmoothOut) pointing at them"""
+    buf = {p: np.empty(shape) for p, shape in shapes.items()}
+    for p, a in buf.items():
+        setattr(out, p, a.ctypes.data_as(C.POINTER(C.c_double)))
+    return buf, out
+
+
+def trace_buffers(parts, lead: tuple, S: int):
+    """(buffers by part, SsmTraceOut) of a traced run: lead = (T,), of a traced batch: (B, T)"""
+    return _out_buffers(abi.SsmTraceOut(), {p: lead + ((S,) if p in ("mean", "var") else ()) for p in parts})
+
+
+def smooth_buffers(parts, lead: tuple, S: int, n: int):
+    """(buffers by part, SsmSmoothOut) of a smoothed run or batch, as trace_buffers"""
+    return _out_buffers(abi.SsmSmoothOut(), {p: lead + ((S, n) if p == "paths" else (S,)) for p in parts})
+
+
+def _by_name(a, cols):
+    return None if a is None else {c: a[..., k].copy() for k, c in enumerate(cols)}
+
+
+def trace_by_name(buf: dict, cols) -> tuple:
+    """trace_buffers' arrays as (ess, mean, var, log_evidence), mean and var as column name -> rows; None: not asked for"""
+    return buf.get("ess"), _by_name(buf.get("mean"), cols), _by_name(buf.get("var"), cols), buf.get("log_evidence")
+
+
+def smooth_by_name(buf: dict, cols) -> tuple:
+    """smooth_buffers' arrays as (paths, mean, var), each column name -> rows (the paths are views); None: not asked for"""
+    paths = {c: buf["paths"][..., k, :] for k, c in enumerate(cols)} if "paths" in buf else None
+    return paths, _by_name(buf.get("mean"), cols), _by_name(buf.get("var"), cols)
+
+
 class SsmTrace:
     """The per-step filtering trace of a scalar-SSM run (include/wsmc.h wsmc_ssm_trace). Row t is
     taken after step t's last observe, before the Resample that follows it: `ess` [T] that
