@@ -57,6 +57,8 @@ def assert_same_state(g, o):
     for k in ("resampled", "weights_changed", "depth", "n_terms", "op_counter", "n_resamples"):
         assert sg[k] == so[k], k
     assert sg["last_ess_perc"] == so["last_ess_perc"] or (math.isnan(sg["last_ess_perc"]) and math.isnan(so["last_ess_perc"]))
+    for d in (-1, so["depth"]):      # the tape (on the persistent route the host writes it)
+        np.testing.assert_array_equal(g.score(d), o.score(d), err_msg=f"score({d})")
 
 
 def same_float(a, b):

@@ -21,7 +21,14 @@ checks the oracle (CPU) and, under -m gpu, the HIP library through the C ABI:
       (−π, π) 1-D moves;
   (e) C5's priors (HalfNormal = Truncated(Normal(0, σ), 0, Inf), Uniform(−π, π)) and its
       oscillator Observe term A·exp(−γt)·cos(ωt + ϕ) (examples/damped_oscillator.jl:11, 24-43),
-      evaluated directly (the build rolls a phasor).
+      evaluated directly (the build rolls a phasor, DESIGN.md §2);
+  (f) one step of the 1D linear-Gaussian SSM (benchmarks/ssm/WeightedSampling/lgssm1d.jl:18-24)
+      through the fused run (wsmc_lgssm1d_run; on the device the persistent workgroup): x0 =
+      x0_std z, x' = a x + q z, y_t => Normal(x', r) with q, r and x0_std STANDARD DEVIATIONS and a
+      the multiplier, then the Resample and the gather. A fused run cannot be stopped between
+      steps, so step t is taken between the runs of data[:t-1] and data[:t] on fresh contexts
+      (run_lgssm_checked; its cases are tests/lgssmfuzz.py's, see tests/test_lgssm_random_runs.py
+      and tests/test_gpu_lgssm_random_runs.py).
 
 Tolerances (written here, the north star's bar is 1e-6 relative on log-weights):
   * draws, columns, log-weights, scores: |a − b| ≤ 1e-12 · max(1, |b|)   (libm vs restated ulps)
@@ -368,6 +375,61 @@ def test_oscillator_matches_reference_math_oracle(scheme):
 def test_oscillator_full_horizon_matches_reference_math_hip(scheme, gpu_available):
     """C5's 60 observations (the rotation blocks included), one sweep per step."""
     assert run_oscillator_checked("hip", 16_384, 60, 1, scheme) <= 4
+
+
+# ---------------------------------------------------------------------------------------
+# (f) the 1D linear-Gaussian SSM step through the fused run
+# ---------------------------------------------------------------------------------------
+def _lgssm_prefix(backend, n, data, kw, seed):
+    """The run of `data` on a fresh context: x, the weights, n_resamples, the last step's (flag,
+    ESS%), the log evidence and the last ancestors. oracle: models.lgssm1d_statements with the last
+    Resample's return recorded; hip: lgssm1d_run(..., ess_trace=True), on the persistent route."""
+    import lgssmfuzz as lf
+    from wsmc.models import lgssm1d_statements
+    if backend == "oracle":
+        ctx = lf._recording()(n, seed=seed)
+        flags = lgssm1d_statements(ctx, data, **kw)
+        flag, ess = ctx.resamples[-1]
+        assert flag == flags[-1]
+    else:
+        ctx = wsmc.Context(n, seed=seed)
+        _, trace = ctx.lgssm1d_run(data, ess_trace=True, **kw)
+        st = ctx.lgssm_stats()
+        assert (st["persistent_runs"], st["statement_runs"]) == (1, 0), st
+        flag, ess = bool(ctx.get_state()["resampled"]), float(trace[-1])
+    out = dict(x=ctx.col_download(ctx.col_find("x")), w=ctx.weights_download(), n_rs=ctx.get_state()["n_resamples"],
+               flag=bool(flag), ess=ess, ev=ctx.log_evidence(), anc=ctx.last_ancestors())
+    ctx.close()
+    return out
+
+
+def run_lgssm_checked(backend, n, data, a, q, r, x0_std, ess_min, scheme=wsmc.RESAMPLE_STRATIFIED, seed=SEED):
+    """Every step t = 1 .. T (T <= 6) of the fused run restated with tests/refmath.py alone from the
+    state the run of data[:t-1] left (t = 1: the prior draw, restated too, and zero weights): q, r and
+    x0_std are standard deviations and a the multiplier here by this file's own arithmetic, whatever
+    the shared headers and the kernel's host-computed (c, rh) pair do with them. Returns (steps that
+    resampled, ancestor ties)."""
+    data = np.asarray(data, dtype=float)
+    assert 1 <= len(data) <= 6
+    kw = dict(a=a, q=q, r=r, x0_std=x0_std, ess_perc_min=ess_min, scheme=scheme)
+    idx = np.arange(n, dtype=np.uint64)
+    x, w, n_rs = x0_std * R.normal_k(seed, 0, idx, 0), np.zeros(n), 0     # op 0: the prior; op 1: its Resample, a no-op
+    ties = 0
+    for t in range(1, len(data) + 1):
+        op = 2 + 3 * (t - 1)                    # the Sample; op + 1 a no-op Resample; op + 2 the Resample
+        xn = a * x + q * R.normal_k(seed, op, idx, 0)
+        lw = w + R.normal_logpdf(data[t - 1], xn, r)
+        ref = RefResample(lw, ess_min, seed, op + 2, scheme)
+        got = _lgssm_prefix(backend, n, data[:t], kw, seed)
+        rs = got["flag"]
+        assert got["n_rs"] == n_rs + int(rs), f"n_resamples at t={t}"
+        out = dict(ess=got["ess"], rs=rs, ev=got["ev"], w=got["w"] if rs else lw,
+                   anc=got["anc"] if rs else None, id=got["anc"].astype(np.float64) if rs else None)
+        ties += check_against_reference("model", lw, out, ref, ess_min)
+        _assert_close(got["x"], xn[got["anc"]] if rs else xn, f"x at t={t}")
+        _assert_close(got["w"], np.full(n, ref.mean) if rs else lw, f"log-weights at t={t}")
+        x, w, n_rs = got["x"], got["w"], got["n_rs"]
+    return n_rs, ties
 
 
 # ---------------------------------------------------------------------------------------

@@ -134,7 +134,10 @@ class Expr:
             else:   # a product of two particle columns: a general expression
                 return Fx.lift(self) * Fx.lift(k)
         k = float(k)
-        scaled = Expr(self.c0 * k, tuple((n, c, coef * k) for n, c, coef in self.terms))
+        # k * x has no constant: with k = +-inf or NaN the absent one stays 0.0 (0.0 * inf would put a
+        # NaN into every particle's value, where inf * x is +-inf)
+        c0 = 0.0 if (self.c0 == 0.0 and self.terms and not math.isfinite(k)) else self.c0 * k
+        scaled = Expr(c0, tuple((n, c, coef * k) for n, c, coef in self.terms))
         # k (c0 + coef x + ...) distributes exactly for a constant, k = +-2^n, or k * x alone
         exact = self.fx is None and (not self.terms or _pow2(k) or
                                      (len(self.terms) == 1 and self.c0 == 0.0 and self.terms[0][2] == 1.0))
