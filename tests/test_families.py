@@ -27,6 +27,8 @@ CASES = {
     "geometric": (lambda: wsmc.Geometric(0.25), stats.geom(0.25, loc=-1), [0.0, 1.0, 7.0, 2.5, -1.0]),
 }
 DISCRETE = ("bernoulli", "bernoulli_logit", "geometric")
+# a finite log-density against its reference (tests/test_math_edges.py holds its corpus to the same)
+LOGPDF_RTOL, LOGPDF_ATOL = 5e-14, 1e-15
 
 
 def observe_at(kernel, xs):
@@ -45,7 +47,7 @@ def test_logpdf_matches_scipy(name):
     finite = np.isfinite(want)
     assert np.array_equal(np.isfinite(got), finite), (got, want)
     assert np.all(got[~finite] == -np.inf)
-    np.testing.assert_allclose(got[finite], want[finite], rtol=5e-14, atol=1e-15)
+    np.testing.assert_allclose(got[finite], want[finite], rtol=LOGPDF_RTOL, atol=LOGPDF_ATOL)
 
 
 @pytest.mark.parametrize("name", sorted(CASES))

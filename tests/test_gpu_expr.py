@@ -6,6 +6,7 @@ the multi-device handle, and the host-side refusals through the C ABI."""
 import numpy as np
 import pytest
 
+import mathedge
 import wsmc
 from oracle import Oracle
 from wsmc import abi, dsl, models
@@ -29,6 +30,10 @@ EXPRS = {
     "abs_neg": lambda: abs(Col("a")) - (-Col("d")),
     # |e| from 1e5 to 1e300: the Payne-Hanek reduction past 2^19 pi/2 (include/wsmc_math.h)
     "sincos_large": lambda: sin(Col("e")) - 2.0 * cos(Col("e")),
+    # tests/mathedge.py's hard arguments, permuted among ordinary ones (fill's columns me, ml, mt)
+    "edge_exp": lambda: exp(Col("me")),
+    "edge_log": lambda: log(Col("ml")),
+    "edge_trig": lambda: sin(Col("mt")) - 2.0 * cos(Col("mt")),
 }
 
 
@@ -38,6 +43,8 @@ def fill(ctx, N, seed=3):
             "d": rng.normal(0.0, 30.0, N),
             "e": np.exp(rng.uniform(np.log(1e5), np.log(1e300), N)) * rng.choice([-1.0, 1.0], N)}
     vals["a"][:4] = [-0.0, 0.0, np.nan, np.inf]
+    for name, op in (("me", "exp"), ("ml", "log"), ("mt", "sin")):   # repeated (or cut) to N
+        vals[name] = np.resize(mathedge.operator_inputs(mathedge.OPERATORS[op])["mixed"][0], N)
     for name, v in vals.items():
         ctx.col_upload(ctx.col_create(name), v)
     ctx.col_upload(ctx.col_create("v", 2), np.stack([rng.normal(size=N), rng.normal(size=N)]))

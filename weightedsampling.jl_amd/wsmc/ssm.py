@@ -312,9 +312,10 @@ class SSM:
         also takes backend.weighted_moments of every column and backend.log_evidence() between each
         step's last observe and its Resample and returns (flags, ESS%, SsmTrace): the definition
         of what Context.ssm_run(trace=True) returns. smooth=True (with wait) also keeps every
-        column's values at each trace point in a column of their own, `name@t`, which the Resamples
-        that follow gather like any other, and reads them after the last step: the result gains an
-        SsmSmooth as its last member, the definition of what Context.ssm_run(smooth=True) returns."""
+        column's values at each trace point in a column of their own, `name@t` (an exact copy, a -0.0
+        included), which the Resamples that follow gather like any other, and reads them after the
+        last step: the result gains an SsmSmooth as its last member, the definition of what
+        Context.ssm_run(smooth=True) returns."""
         if trace and not wait:
             raise ValueError("trace=True needs wait=True (the trace point is a synchronisation)")
         if smooth and not wait:
@@ -412,8 +413,10 @@ class SSM:
                 lev[t] = backend.log_evidence()
             if smooth:
                 hs = [backend.col_create(f"{name}@{t}", 1) for name in self.cols]
-                for h, i in zip(hs, ids):
-                    backend.assign(h, [Operand.column(i)])
+                for h, i in zip(hs, ids):   # a copy, bit for bit: the affine form 0.0 + 1.0 x would turn a -0.0 into 0.0
+                    copy = (abi.XInst * 1)()
+                    copy[0].op, copy[0].col, copy[0].comp = abi.X_COL, i, 0
+                    backend.assign_expr(h, copy, [1])
                 hist.append(hs)
 
         for t in range(T):
