@@ -1204,20 +1204,30 @@ WSMC_HD double wsmc_es_key(uint64_t seed, uint64_t op, uint64_t i, uint64_t q) {
 WSMC_HD double wsmc_linspace_edge(double lo, double hi, int k, int n) {
     if (k == 0) return lo;
     if (k == n) return hi;
+    /* finite extremes whose difference overflows (Base's _linspace handles that case as well):
+       the edge of the halved extremes, doubled. Both extremes are above 2^970 in magnitude then,
+       so halving is exact, and the edge lies between them, so doubling is: the same value. */
+    const int wide = lo - lo == 0.0 && hi - hi == 0.0 && !((hi - lo) - (hi - lo) == 0.0);
+    if (wide) {
+        lo *= 0.5;
+        hi *= 0.5;
+    }
     /* hi - lo = d + e exactly (TwoSum) */
     const double d = hi - lo;
     const double bb = d - hi;
     const double e = (hi - (d - bb)) + (-lo - bb);
-    /* k (d + e) / n: k d exactly as p + pe (fma), then / n (n a power of two: exact) */
-    const double p = (double)k * d;
-    const double pe = __builtin_fma((double)k, d, -p);
-    const double inv = 1.0 / (double)n;
-    const double s_hi = p * inv, s_lo = (pe + (double)k * e) * inv;
+    /* (k / n) (d + e): n is a power of two, so c = k / n is exact, and below 1, so c d cannot
+       overflow where k d would (a difference above DBL_MAX / 7); c d exactly as p + pe (fma) */
+    const double c = (double)k * (1.0 / (double)n);
+    const double p = c * d;
+    const double pe = __builtin_fma(c, d, -p);
+    const double s_hi = p, s_lo = pe + c * e;
     /* lo + s_hi + s_lo, rounded once (TwoSum of lo + s_hi, then the tails) */
     const double t = lo + s_hi;
     const double tb = t - lo;
     const double te = (lo - (t - tb)) + (s_hi - tb);
-    return t + (te + s_lo);
+    const double r = t + (te + s_lo);
+    return wide ? 2.0 * r : r;
 }
 WSMC_HD int wsmc_hist_bin(double v, const double* edges, int nbins) {
     int c = 0;                                   /* searchsortedlast: #edges <= v */

@@ -1173,21 +1173,32 @@ def _moments_close(o, s, a, b) -> bool:
     the order of N-term sums only. A sum of N terms in any order is within (N - 1) eps sum|v_i| of
     the exact one, so with z = max|expr| the means (two sums and a quotient, both sides) agree
     within 8 N eps z, and the centred second moments (terms <= (2 z)^2, plus 4 z times the means'
-    difference) within 64 N eps z^2."""
+    difference) within 64 N eps z^2. z is taken over the expressions whose values are all finite (a
+    finite component involves no other); a component that is not finite on either side must be the
+    same NaN or the same infinity on both."""
     n, eps = o.n, np.finfo(float).eps
-    z = []
+    zm = 0.0
     for e in s.exprs:
         v = np.full(n, e.c0)
         for name, comp, coef in e.terms:
             c = o.col_download(o.col_find(name))
             v = v + coef * (c[comp] if c.ndim > 1 else c)
-        z.append(float(np.max(np.abs(v))))
-    zm = max(z)
+        if np.isfinite(v).all():
+            zm = max(zm, float(np.max(np.abs(v))))
+
+    def close(x, y, tol):
+        x, y = np.asarray(x, dtype=np.float64).ravel(), np.asarray(y, dtype=np.float64).ravel()
+        if x.shape != y.shape:
+            return False
+        fin = np.isfinite(x) & np.isfinite(y)
+        rest = (x.view(np.uint64) == y.view(np.uint64)) | (np.isnan(x) & np.isnan(y))
+        with np.errstate(invalid="ignore"):
+            return bool(np.all(np.where(fin, np.abs(x - y) <= tol, rest)))
+
     (ma, ca), (mb, cb) = a, b
-    ok = bool(np.all(np.abs(np.asarray(ma) - np.asarray(mb)) <= 8 * n * eps * zm))
+    ok = close(ma, mb, 8 * n * eps * zm)
     if ca is not None or cb is not None:
-        ok = ok and ca is not None and cb is not None and \
-            bool(np.all(np.abs(np.asarray(ca) - np.asarray(cb)) <= 64 * n * eps * zm * zm))
+        ok = ok and ca is not None and cb is not None and close(ca, cb, 64 * n * eps * zm * zm)
     return ok
 
 

@@ -1,6 +1,8 @@
 """Analysis reductions (src/utils.jl): expectation / @E, describe's weighted mean and std
 (corrected=false), min/max, ESS. The oracle is checked against numpy here (CPU); the HIP
-path against the oracle bit for bit (-m gpu)."""
+path against the oracle bit for bit (-m gpu). The directed corpus of these reads (signed zeros,
+NaN and infinite values and weights, ties, the sizes at which a kernel's structure changes, shard
+splits) is tests/readedge.py, run by tests/test_read_edges.py and tests/test_gpu_read_edges.py."""
 import math
 
 import numpy as np
