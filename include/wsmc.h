@@ -445,8 +445,15 @@ int wsmc_debug_lgssm(wsmc_ctx* ctx, int32_t segment_steps, int64_t* stats_out);
  *   ASSIGN_EXPR  col .= prog[0 .. prog_len)      (wsmc_assign_expr: one postfix program of at
  *                                                 most WSMC_SSM_XPROG_MAX instructions)
  *   OBSERVE      value => dist                   (wsmc_observe)
- * A Resample(ess_perc_min, scheme) follows every SAMPLE and every OBSERVE (what @model inserts);
- * it takes its op counter whether or not it runs, and runs only if the weights changed.
+ *   SAMPLE_IMPORTANCE  col ~ importance_kernel(dist, target)   (wsmc_sample_importance: `dist` is
+ *                                                 the proposal; the weights gain
+ *                                                 logpdf(target, x) - logpdf(dist, x), both dists'
+ *                                                 operands read after x is stored, so one that
+ *                                                 names `col` sees the new value)
+ *   WEIGHT       _ ~ dist, scored at value       (wsmc_weight; OBSERVE's fields)
+ * A Resample(ess_perc_min, scheme) follows every SAMPLE, OBSERVE, SAMPLE_IMPORTANCE and WEIGHT
+ * (what @model inserts); it takes its op counter whether or not it runs, and runs only if the
+ * weights changed. The trace point of a traced or smoothed run stays the step's last OBSERVE.
  * dists: dim 1, WSMC_MEAN_AFFINE, family NORMAL, HALFNORMAL, UNIFORM, 5 .. 14 or 16 .. 23.
  * Data: the call takes a row-major T x data_dim table (data_dim <= WSMC_SSM_MAX_DATA). In an
  * operand of `step` at most one slot k may have col[k] == WSMC_OPERAND_DATA with comp[k] = j <
@@ -462,16 +469,18 @@ int wsmc_debug_lgssm(wsmc_ctx* ctx, int32_t segment_steps, int64_t* stats_out);
 #define WSMC_SSM_NAME_MAX 32
 #define WSMC_OPERAND_DATA (-2)
 typedef enum {
-    WSMC_SSM_SAMPLE = 0, WSMC_SSM_ASSIGN = 1, WSMC_SSM_ASSIGN_EXPR = 2, WSMC_SSM_OBSERVE = 3
+    WSMC_SSM_SAMPLE = 0, WSMC_SSM_ASSIGN = 1, WSMC_SSM_ASSIGN_EXPR = 2, WSMC_SSM_OBSERVE = 3,
+    WSMC_SSM_SAMPLE_IMPORTANCE = 4, WSMC_SSM_WEIGHT = 5
 } wsmc_ssm_kind;
 typedef struct {
     int32_t kind;               /* wsmc_ssm_kind */
     int32_t col;                /* SAMPLE, ASSIGN, ASSIGN_EXPR: the output column (local index) */
     int32_t prog_len;           /* ASSIGN_EXPR: instructions of prog */
     int32_t reserved;
-    wsmc_dist dist;             /* SAMPLE, OBSERVE */
-    wsmc_operand value;         /* ASSIGN: the right-hand side; OBSERVE: the observed value */
+    wsmc_dist dist;             /* SAMPLE, OBSERVE, WEIGHT; SAMPLE_IMPORTANCE: the proposal */
+    wsmc_operand value;         /* ASSIGN: the right-hand side; OBSERVE, WEIGHT: the scored value */
     wsmc_xinst prog[WSMC_SSM_XPROG_MAX];
+    wsmc_dist target;           /* SAMPLE_IMPORTANCE: the target (last, so every other offset holds) */
 } wsmc_ssm_stmt;
 typedef struct {
     int32_t n_cols;             /* 1 .. WSMC_SSM_MAX_COLS */
@@ -618,7 +627,8 @@ int wsmc_ssm_smooth_sizeof(int64_t* bytes);
  * resampling, a sharded or multi-device handle, weights_changed set, more than WSMC_XPROG_MAX
  * program instructions. smooth NULL, or every member NULL: wsmc_ssm_run_traced.
  * The call allocates, for its duration, 8 T n n_cols bytes for the history, 4 T n n_obs for the
- * ancestor log (n_obs: the OBSERVEs of a step) and 16 T n_cols + 4 T n_obs for the rows and the
+ * ancestor log (n_obs: the OBSERVEs, WEIGHTs and importance SAMPLEs of a step: the Resamples
+ * that can run) and 16 T n_cols + 4 T n_obs for the rows and the
  * log's flags; WSMC_ENOMEM (the context as it was) when the device refuses them. */
 int wsmc_ssm_run_smoothed(wsmc_ctx* ctx, const wsmc_ssm_spec* spec, const double* data, int32_t T,
                           double ess_perc_min, int32_t scheme, double* log_evidence_out,

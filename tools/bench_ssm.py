@@ -37,7 +37,17 @@ smooth=True) on a Context with the lazy store. The routes alternate inside a rou
 each route on fresh contexts (made before the clock starts) as often as fills half a second; the
 figure is the median over three rounds after a warm-up round, with the rounds' range beside it.
 The device times of the trace-back's two kernels are the library's own (HIP events,
-Context.ssm_smooth_stats). Lines go to profiles/ssm_smooth.jsonl."""
+Context.ssm_smooth_stats). Lines go to profiles/ssm_smooth.jsonl.
+
+    python tools/bench_ssm.py --guided                   lgssm1d_guided at T = 1e3, 1e4, 1e5
+    python tools/bench_ssm.py --guided --T 10000
+
+The guided leg (an importance Sample a step: the guided kernels), forced resampling, the smooth
+leg's protocol (alternating routes, rounds of half a second, the median of three rounds after a
+warm-up round with their range): models.lgssm1d_guided() through Context.ssm_run, through
+spec.statements on a Context (asynchronous Resamples) and through the library's statement loop
+(a foreign column present), and models.lgssm1d_spec() through Context.ssm_run for scale (the
+bootstrap filter of the same model on the unguided kernel). Lines go to profiles/ssm_guided.jsonl."""
 import argparse
 import json
 import pathlib
@@ -53,6 +63,7 @@ LEGS = ["sv", "poisson_count", "kitagawa", "local_trend", "lgssm"]
 OUT = ROOT / "profiles" / "ssm_fused.jsonl"
 OUT_TRACE = ROOT / "profiles" / "ssm_trace.jsonl"
 OUT_SMOOTH = ROOT / "profiles" / "ssm_smooth.jsonl"
+OUT_GUIDED = ROOT / "profiles" / "ssm_guided.jsonl"
 
 
 def best_of(run, reps=2):
@@ -271,14 +282,78 @@ def child_smooth(leg: str, T: int) -> dict:
     return out
 
 
-def driver(Ts, legs, trace=False, smooth=False) -> int:
-    out = OUT_SMOOTH if smooth else OUT_TRACE if trace else OUT
+def child_guided(T: int) -> dict:
+    import statistics
+    import wsmc
+    from wsmc import models
+    guided, boot, data = models.lgssm1d_guided(), models.lgssm1d_spec(), models.lgssm1d_data(T)
+    guided.check()
+    last = {}
+
+    def fused(spec, name):
+        def run(ctx):
+            ctx.ssm_run(spec, data, ess_perc_min=1.0, want_evidence=False)
+            assert ctx.ssm_stats()["persistent_runs"] == 1
+            last[name] = (ctx.log_evidence(), ctx.get_state()["n_resamples"])
+        return run
+
+    def statements(ctx):
+        guided.statements(ctx, data, ess_perc_min=1.0, wait=False)
+        ctx.sync()
+        last["guided_statements"] = (ctx.log_evidence(), ctx.get_state()["n_resamples"])
+
+    def statements_lib(ctx):
+        ctx.ssm_run(guided, data, ess_perc_min=1.0, want_evidence=False)
+        assert ctx.ssm_stats()["statement_runs"] == 1
+        last["guided_statements_lib"] = (ctx.log_evidence(), ctx.get_state()["n_resamples"])
+
+    routes = {"guided_persistent": fused(guided, "guided_persistent"), "guided_statements": statements,
+              "guided_statements_lib": statements_lib, "lgssm_persistent": fused(boot, "lgssm_persistent")}
+    times = {k: [] for k in routes}
+    reps = {k: 1 for k in routes}
+    for rnd in range(5):   # round 0 warms up, round 1 sizes the windows, rounds 2..4 are the figures
+        for name, run in routes.items():
+            ctxs = [wsmc.Context(N, seed=42) for _ in range(reps[name])]
+            for c in ctxs:
+                if name == "guided_statements_lib":   # a foreign column: the statement route
+                    c.assign(c.col_create("_other", 1), models._const([0.0]))
+                c.sync()
+            t0 = time.perf_counter()
+            for c in ctxs:
+                run(c)
+            dt = (time.perf_counter() - t0) / len(ctxs)
+            for c in ctxs:
+                c.close()
+            if rnd == 1:
+                reps[name] = max(1, min(64, int(0.5 / dt) + 1))
+            if rnd >= 2:
+                times[name].append(dt)
+    # the three guided routes compute the same thing; every Resample after an OBSERVE ran
+    assert last["guided_persistent"] == last["guided_statements"] == last["guided_statements_lib"], last
+    assert last["guided_persistent"][1] >= T and last["lgssm_persistent"][1] == T, last
+    med = {k: statistics.median(v) for k, v in times.items()}
+    out = {"leg": "lgssm1d_guided", "N": N, "T": T, "columns": len(guided.cols), "step_statements": guided.spec.n_step,
+           "runs_per_round": reps, "log_evidence": last["guided_persistent"][0], "resamples": last["guided_persistent"][1],
+           "lgssm_log_evidence": last["lgssm_persistent"][0]}
+    for k in routes:
+        out[f"{k}_s"] = med[k]
+        out[f"{k}_s_range"] = [min(times[k]), max(times[k])]
+        out[f"{k}_us_per_step"] = 1e6 * med[k] / T
+    out.update(factor_vs_statements=med["guided_statements"] / med["guided_persistent"],
+               factor_vs_statements_lib=med["guided_statements_lib"] / med["guided_persistent"],
+               guided_over_lgssm=med["guided_persistent"] / med["lgssm_persistent"])
+    return out
+
+
+def driver(Ts, legs, trace=False, smooth=False, guided=False) -> int:
+    out = OUT_GUIDED if guided else OUT_SMOOTH if smooth else OUT_TRACE if trace else OUT
     OUT.parent.mkdir(exist_ok=True)
     for leg in legs:
         per_step = None   # seconds a step of one child (all its routes and repetitions), from the run before
         for T in Ts:
             limit = 180 if per_step is None else int(60 + 3 * per_step * T)
-            cmd = ["timeout", "-k", "10", str(limit), sys.executable, __file__, "--leg", leg, "--T", str(T)]
+            cmd = ["timeout", "-k", "10", str(limit), sys.executable, __file__, "--T", str(T)]
+            cmd += ["--guided"] if guided else ["--leg", leg]
             cmd += ["--trace"] if trace else []
             cmd += ["--smooth"] if smooth else []
             t0 = time.perf_counter()
@@ -303,7 +378,13 @@ if __name__ == "__main__":
     ap.add_argument("--legs", default=",".join(LEGS))
     ap.add_argument("--trace", action="store_true", help="the trace leg (profiles/ssm_trace.jsonl)")
     ap.add_argument("--smooth", action="store_true", help="the smooth leg (profiles/ssm_smooth.jsonl)")
+    ap.add_argument("--guided", action="store_true", help="the guided leg (profiles/ssm_guided.jsonl)")
     a = ap.parse_args()
+    if a.guided and a.T and len(a.T) == 1:
+        print(json.dumps(child_guided(a.T[0])), flush=True)
+        sys.exit(0)
+    if a.guided:
+        sys.exit(driver(a.T or [1000, 10_000, 100_000], ["lgssm1d_guided"], guided=True))
     if a.leg:
         print(json.dumps((child_smooth if a.smooth else child_trace if a.trace else child)(a.leg, (a.T or [1000])[0])), flush=True)
         sys.exit(0)

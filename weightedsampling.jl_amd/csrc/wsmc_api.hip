@@ -780,7 +780,7 @@ int wsmc_destroy(wsmc_ctx* c) {
                     c->d_colptr, c->run_params, c->d_tape, c->run_max, c->run_rec, c->run_dec, c->anc_log, c->obs_buf, c->run_grp, c->run_rg, c->run_nfix, c->run_wcnt, c->run_w0,
                     c->vscratch, c->xscratch, c->xp, c->comb, c->anc_out, c->xbuf, c->d_comp, c->d_ctape, c->d_prog, c->rs_grp[0], c->rs_grp[1], c->rs_qs,
                     c->xpairs, c->xnb, c->xwin, c->xstat, c->w_save, c->xms, c->xanc, c->xlines, c->xpeer,
-                    c->lg_data, c->lg_trace, c->lg_rec, c->ssm_rows};
+                    c->lg_data, c->lg_trace, c->lg_rec, c->ssm_rows, c->ssm_targets};
     for (void* p : bufs)
         if (p) (void)hipFree(p);
     for (double* p : c->xrun)
@@ -5401,20 +5401,29 @@ static const char* ssm_operand_why(const wsmc_ssm_spec* sp, const wsmc_operand& 
     if (ndata == 1 && !(o.c0 == 0.0)) return "a data reference needs c0 == 0";
     return nullptr;
 }
+// a statement's kind by what it holds: a Sample (plain or importance) writes a column from a draw,
+// a weighing statement (OBSERVE, WEIGHT) scores `value` under `dist`
+static bool ssm_is_sample(int32_t kind) { return kind == WSMC_SSM_SAMPLE || kind == WSMC_SSM_SAMPLE_IMPORTANCE; }
+static bool ssm_is_weigh(int32_t kind) { return kind == WSMC_SSM_OBSERVE || kind == WSMC_SSM_WEIGHT; }
+// whether the Resample that follows the statement can run inside a run (the weights changed)
+static bool ssm_resamples(int32_t kind) { return ssm_is_weigh(kind) || kind == WSMC_SSM_SAMPLE_IMPORTANCE; }
+static const char* ssm_dist_why(const wsmc_ssm_spec* sp, const wsmc_dist& d, bool step) {
+    if (!ssm_family_ok(d.family)) return "a family that is not a scalar one (or unknown)";
+    if (d.dim != 1) return "a dist of dim != 1";
+    if (d.mean_fn != WSMC_MEAN_AFFINE) return "a mean function other than WSMC_MEAN_AFFINE";
+    for (int k = 0; k < 4; ++k)
+        if (const char* w = ssm_operand_why(sp, d.mu[k], step)) return w;
+    return ssm_operand_why(sp, d.scale, step);
+}
 static const char* ssm_stmt_why(const wsmc_ssm_spec* sp, const wsmc_ssm_stmt& s, bool step) {
-    const bool dist = s.kind == WSMC_SSM_SAMPLE || s.kind == WSMC_SSM_OBSERVE;
+    const bool dist = ssm_is_sample(s.kind) || ssm_is_weigh(s.kind);
     if (!dist && s.kind != WSMC_SSM_ASSIGN && s.kind != WSMC_SSM_ASSIGN_EXPR) return "an unknown statement kind";
-    if (s.kind != WSMC_SSM_OBSERVE && (s.col < 0 || s.col >= sp->n_cols)) return "an output column index past n_cols";
-    if (dist) {
-        const wsmc_dist& d = s.dist;
-        if (!ssm_family_ok(d.family)) return "a family that is not a scalar one (or unknown)";
-        if (d.dim != 1) return "a dist of dim != 1";
-        if (d.mean_fn != WSMC_MEAN_AFFINE) return "a mean function other than WSMC_MEAN_AFFINE";
-        for (int k = 0; k < 4; ++k)
-            if (const char* w = ssm_operand_why(sp, d.mu[k], step)) return w;
-        if (const char* w = ssm_operand_why(sp, d.scale, step)) return w;
-    }
-    if (s.kind == WSMC_SSM_ASSIGN || s.kind == WSMC_SSM_OBSERVE)
+    if (!ssm_is_weigh(s.kind) && (s.col < 0 || s.col >= sp->n_cols)) return "an output column index past n_cols";
+    if (dist)
+        if (const char* w = ssm_dist_why(sp, s.dist, step)) return w;
+    if (s.kind == WSMC_SSM_SAMPLE_IMPORTANCE)
+        if (const char* w = ssm_dist_why(sp, s.target, step)) return w;
+    if (s.kind == WSMC_SSM_ASSIGN || ssm_is_weigh(s.kind))
         if (const char* w = ssm_operand_why(sp, s.value, step)) return w;
     if (s.kind == WSMC_SSM_ASSIGN_EXPR) {
         if (s.prog_len < 1 || s.prog_len > WSMC_SSM_XPROG_MAX) return "a program of less than 1 or more than WSMC_SSM_XPROG_MAX instructions";
@@ -5496,23 +5505,30 @@ struct SsmShape {
     int nprog;                    // program instructions over the whole spec
     unsigned feat;                // WSMC_FEAT_ bits over its dists (the kernel's instantiation)
     int n_obs, last_obs;          // a step's OBSERVEs, and the last one (its Resample's ESS% is the trace's)
-    int init_ops, step_ops;       // op counters `init` / one step take: 2 a SAMPLE (its Resample's too), 1 an OBSERVE
-    int init_terms, step_terms;   // tape terms `init` / one step leave: one a SAMPLE, one an OBSERVE
+    int init_ops, step_ops;       // op counters `init` / one step take: 2 a SAMPLE of either kind (its Resample's too), 1 an OBSERVE or WEIGHT
+    int init_terms, step_terms;   // tape terms `init` / one step leave: one a SAMPLE of either kind, one an OBSERVE or WEIGHT
+    bool guided;                  // an importance Sample or a WEIGHT anywhere: the guided kernels run it
+    int n_slots, trace_slot;      // a smoothed run's log: the Resamples of a step that can run (after OBSERVE, WEIGHT, importance
+                                  // SAMPLE), and the last OBSERVE's among them (without the new kinds: n_obs and n_obs - 1)
 };
 static SsmShape ssm_shape(const wsmc_ssm_spec* sp) {
-    SsmShape h = {sp->n_cols, sp->data_dim, sp->n_init, sp->n_step, 0, 0u, 0, -1, 0, 0, 0, 0};
+    SsmShape h = {sp->n_cols, sp->data_dim, sp->n_init, sp->n_step, 0, 0u, 0, -1, 0, 0, 0, 0, false, 0, -1};
     for (int q = 0; q < sp->n_init + sp->n_step; ++q) {
         const bool step = q >= sp->n_init;
         const wsmc_ssm_stmt& s = step ? sp->step[q - sp->n_init] : sp->init[q];
-        const bool sample = s.kind == WSMC_SSM_SAMPLE, observe = s.kind == WSMC_SSM_OBSERVE;
+        const bool sample = ssm_is_sample(s.kind), weigh = ssm_is_weigh(s.kind);
         if (s.kind == WSMC_SSM_ASSIGN_EXPR) h.nprog += s.prog_len;
-        if (sample || observe) h.feat |= wsmc_dist_feat(&s.dist);
-        (step ? h.step_ops : h.init_ops) += sample ? 2 : observe ? 1 : 0;
-        (step ? h.step_terms : h.init_terms) += sample || observe;
-        if (step && observe) {
+        if (sample || weigh) h.feat |= wsmc_dist_feat(&s.dist);
+        if (s.kind == WSMC_SSM_SAMPLE_IMPORTANCE) h.feat |= wsmc_dist_feat(&s.target);
+        h.guided |= s.kind == WSMC_SSM_SAMPLE_IMPORTANCE || s.kind == WSMC_SSM_WEIGHT;
+        (step ? h.step_ops : h.init_ops) += sample ? 2 : weigh ? 1 : 0;
+        (step ? h.step_terms : h.init_terms) += sample || weigh;
+        if (step && s.kind == WSMC_SSM_OBSERVE) {
             h.n_obs += 1;
             h.last_obs = q - sp->n_init;
+            h.trace_slot = h.n_slots;
         }
+        if (step && ssm_resamples(s.kind)) h.n_slots += 1;
     }
     return h;
 }
@@ -5531,6 +5547,11 @@ static int ssm_issue(wsmc_ctx* c, const wsmc_ssm_stmt& s, const int32_t* ids, co
         case WSMC_SSM_SAMPLE: {
             const wsmc_dist d = ssm_map_dist(s.dist, ids, row);
             if ((rc = wsmc_sample(c, ids[s.col], &d))) return rc;
+            return wsmc_resample(c, ess_min, scheme, nullptr, nullptr);
+        }
+        case WSMC_SSM_SAMPLE_IMPORTANCE: {
+            const wsmc_dist prop = ssm_map_dist(s.dist, ids, row), targ = ssm_map_dist(s.target, ids, row);
+            if ((rc = wsmc_sample_importance(c, ids[s.col], &prop, &targ))) return rc;
             return wsmc_resample(c, ess_min, scheme, nullptr, nullptr);
         }
         case WSMC_SSM_ASSIGN: {
@@ -5559,7 +5580,7 @@ static int ssm_issue(wsmc_ctx* c, const wsmc_ssm_stmt& s, const int32_t* ids, co
             const wsmc_dist d = ssm_map_dist(s.dist, ids, row);
             wsmc_operand x[4];
             for (int k = 0; k < 4; ++k) x[k] = ssm_map_operand(s.value, ids, row);
-            if ((rc = wsmc_observe(c, &d, x))) return rc;
+            if ((rc = s.kind == WSMC_SSM_WEIGHT ? wsmc_weight(c, &d, x) : wsmc_observe(c, &d, x))) return rc;
             if (mom && (mom->mean || mom->var)) {
                 wsmc_operand e[4];
                 for (int k = 0; k < 4; ++k) {
@@ -5612,14 +5633,14 @@ static SsmStmt ssm_dev_stmt(const wsmc_ssm_stmt& s, SsmIns* ins, int* nins) {
     r.kind = s.kind;
     r.col = s.col;
     r.mu.col[0] = r.mu.col[1] = r.scale.col[0] = r.scale.col[1] = r.value.col[0] = r.value.col[1] = -1;
-    if (s.kind == WSMC_SSM_SAMPLE || s.kind == WSMC_SSM_OBSERVE) {
+    if (ssm_is_sample(s.kind) || ssm_is_weigh(s.kind)) {
         r.family = s.dist.family;
         r.mu = s.dist.mu[0];
         r.scale = s.dist.scale;
         r.param[0] = s.dist.param[0];
         r.param[1] = s.dist.param[1];
     }
-    if (s.kind == WSMC_SSM_ASSIGN || s.kind == WSMC_SSM_OBSERVE) r.value = s.value;
+    if (s.kind == WSMC_SSM_ASSIGN || ssm_is_weigh(s.kind)) r.value = s.value;
     if (s.kind == WSMC_SSM_ASSIGN_EXPR) {
         r.prog = *nins;
         r.prog_len = s.prog_len;
@@ -5638,6 +5659,22 @@ static void ssm_dev_image(const wsmc_ssm_spec* sp, SsmStmt* init, SsmStmt* step,
     int nins = 0;
     for (int q = 0; q < sp->n_init; ++q) init[q] = ssm_dev_stmt(sp->init[q], ins, &nins);
     for (int q = 0; q < sp->n_step; ++q) step[q] = ssm_dev_stmt(sp->step[q], ins, &nins);
+}
+// the targets of a guided spec's importance Samples as the guided kernels read them from device
+// memory: statement q of `init` at [q], of `step` at [WSMC_SSM_MAX_INIT + q] (zero elsewhere)
+static void ssm_dev_targets(const wsmc_ssm_spec* sp, SsmTarget* tg) {
+    std::memset(tg, 0, sizeof(SsmTarget) * kSsmTargets);
+    for (int q = 0; q < sp->n_init + sp->n_step; ++q) {
+        const bool step = q >= sp->n_init;
+        const wsmc_ssm_stmt& s = step ? sp->step[q - sp->n_init] : sp->init[q];
+        if (s.kind != WSMC_SSM_SAMPLE_IMPORTANCE) continue;
+        SsmTarget& r = tg[step ? WSMC_SSM_MAX_INIT + q - sp->n_init : q];
+        r.family = s.target.family;
+        r.mu = s.target.mu[0];
+        r.scale = s.target.scale;
+        r.param[0] = s.target.param[0];
+        r.param[1] = s.target.param[1];
+    }
 }
 // the arguments SsmArgs and SsmBatchArgs share (a segment's own are set_segment's)
 extern "C++" {
@@ -5711,10 +5748,11 @@ struct SsmSmoothBufs {
     double *mean, *var;
     size_t flags_off, flags_bytes;   // the flags (zeroed before the run)
 };
-static size_t ssm_smooth_carve(char* base, const wsmc_ssm_smooth& sm, int64_t B, int64_t T, int64_t n, int S, int n_obs,
+static size_t ssm_smooth_carve(char* base, const wsmc_ssm_smooth& sm, int64_t B, int64_t T, int64_t n, const SsmShape& sh,
                                SsmSmoothBufs* out) {
-    const size_t nhist = ssm_up(sizeof(double) * (size_t)B * T * S * n), nlog = ssm_up(sizeof(int32_t) * (size_t)B * T * n_obs * n),
-                 nflag = ssm_up(sizeof(int32_t) * (size_t)B * T * n_obs), nrow = ssm_up(sizeof(double) * (size_t)B * T * S);
+    const int S = sh.S, n_slots = sh.n_slots;
+    const size_t nhist = ssm_up(sizeof(double) * (size_t)B * T * S * n), nlog = ssm_up(sizeof(int32_t) * (size_t)B * T * n_slots * n),
+                 nflag = ssm_up(sizeof(int32_t) * (size_t)B * T * n_slots), nrow = ssm_up(sizeof(double) * (size_t)B * T * S);
     if (out) {
         char* q = base;
         out->rec.hist = reinterpret_cast<double*>(q); q += nhist;
@@ -5723,8 +5761,10 @@ static size_t ssm_smooth_carve(char* base, const wsmc_ssm_smooth& sm, int64_t B,
         out->flags_off = (size_t)(q - base);
         out->flags_bytes = nflag;
         q += nflag;
-        out->rec.n_obs = n_obs;
+        out->rec.n_slots = n_slots;
         out->rec.T = (int32_t)T;
+        out->rec.trace_slot = sh.trace_slot;
+        out->rec.pad = 0;
         out->mean = sm.mean ? reinterpret_cast<double*>(q) : nullptr; q += sm.mean ? nrow : 0;
         out->var = sm.var ? reinterpret_cast<double*>(q) : nullptr;
     }
@@ -5800,10 +5840,10 @@ static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int
     std::memset(&sb, 0, sizeof(sb));
     if (smooth) {
         WSMC_HIP(hipSetDevice(c->device));
-        const size_t bytes = sm_bytes = ssm_smooth_carve(nullptr, sm, 1, T, c->N, S, sh.n_obs, nullptr);
+        const size_t bytes = sm_bytes = ssm_smooth_carve(nullptr, sm, 1, T, c->N, sh, nullptr);
         if (int rc = ssm_smooth_alloc(&sm_slab, bytes + 256, "ssm smoothed run")) return rc;
         WSMC_HIP(sm_clock.start());
-        ssm_smooth_carve(sm_slab.p, sm, 1, T, c->N, S, sh.n_obs, &sb);
+        ssm_smooth_carve(sm_slab.p, sm, 1, T, c->N, sh, &sb);
     }
     for (int k = 0; k < S; ++k)   // the missing ones, in order
         if (int rc = wsmc_col_create(c, sp->col_names[k], 1, &ids[k])) return rc;
@@ -5830,10 +5870,19 @@ static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int
         WSMC_HIP(hipMemcpyAsync(c->lg_data, data, sizeof(double) * (size_t)ndata, hipMemcpyHostToDevice, c->stream));
     WSMC_HIP(hipMemsetAsync(c->lg_rec, 0, sizeof(LgRecord), c->stream));
     if (smooth) WSMC_HIP(hipMemsetAsync(sm_slab.p + sb.flags_off, 0, sb.flags_bytes, c->stream));
-    SsmRecArgs kra;   // (a smoothed run's launches: the same arguments and the log)
-    std::memset(&kra, 0, sizeof(kra));
+    // (a smoothed run's launches: the same arguments and the log; a guided spec's: and its targets)
+    SsmGuidedArgs kga;
+    std::memset(&kga, 0, sizeof(kga));
+    SsmRecArgs& kra = kga.ra;
     SsmArgs& ka = kra.a;
     kra.r = sb.rec;
+    SsmTarget targets[kSsmTargets];
+    if (sh.guided) {   // the targets to a buffer of the context, ahead of the first launch on the stream
+        if (int rc = ctx_grow(c, &c->ssm_targets, &c->ssm_targets_cap, (int64_t)(sizeof(targets) / sizeof(double)))) return rc;
+        ssm_dev_targets(sp, targets);
+        WSMC_HIP(hipMemcpyAsync(c->ssm_targets, targets, sizeof(targets), hipMemcpyHostToDevice, c->stream));
+        kga.targ = reinterpret_cast<const SsmTarget*>(c->ssm_targets);
+    }
     ka.tr_mean = n_mean ? c->ssm_rows : nullptr;
     ka.tr_var = n_var ? c->ssm_rows + n_mean : nullptr;
     ka.tr_logev = n_le ? c->ssm_rows + n_mean + n_var : nullptr;
@@ -5843,7 +5892,7 @@ static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int
     ka.data = c->lg_data;
     ka.ess_trace = ess_trace_out ? c->lg_trace : nullptr;
     ka.rec = c->lg_rec;
-    const int threads = ssm_threads(feat, (int)c->N);
+    const int threads = sh.guided ? ssm_guided_threads(feat, (int)c->N) : ssm_threads(feat, (int)c->N);
     ssm_fill_args(ka, sh, c->N, threads, scheme, ess_min);
     ka.seed = c->seed;
     ka.op_base = c->op;
@@ -5854,7 +5903,9 @@ static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int
     WSMC_HIP(sm_clock.mark(0, c->stream));
     for (int32_t t0 = 0; t0 < T; t0 += K, ++nseg) {
         set_segment(ka, t0, K, T);
-        if (smooth)
+        if (sh.guided)
+            WSMC_HIP(launch_ssm_guided_segment(c->stream, kga, feat, threads, smooth));
+        else if (smooth)
             WSMC_HIP(launch_ssm_segment_rec(c->stream, kra, feat, threads));
         else
             WSMC_HIP(launch_ssm_segment(c->stream, ka, feat, threads));
@@ -5885,14 +5936,14 @@ static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int
     gc_log(c);
     c->tape.reserve(c->tape.size() + (size_t)sh.init_terms + (size_t)sh.step_terms * (size_t)T);
     auto book = [&](const wsmc_ssm_stmt& s, const double* row) {
-        if (s.kind == WSMC_SSM_SAMPLE) {
-            push_sample_term(c, ids[s.col], ssm_map_dist(s.dist, ids, row));
-        } else if (s.kind == WSMC_SSM_OBSERVE) {
+        if (ssm_is_sample(s.kind)) {   // an importance Sample leaves its target
+            push_sample_term(c, ids[s.col], ssm_map_dist(s.kind == WSMC_SSM_SAMPLE ? s.dist : s.target, ids, row));
+        } else if (ssm_is_weigh(s.kind)) {
             wsmc_term ob;
             std::memset(&ob, 0, sizeof(ob));
             ob.dist = ssm_map_dist(s.dist, ids, row);
             for (int k = 0; k < 4; ++k) ob.x[k] = ssm_map_operand(s.value, ids, row);
-            ob.kind = WSMC_TERM_OBSERVE;
+            ob.kind = s.kind == WSMC_SSM_WEIGHT ? WSMC_TERM_WEIGHT : WSMC_TERM_OBSERVE;
             ob.depth = c->depth;
             c->tape.push_back(ob);
         }
@@ -5958,21 +6009,30 @@ static std::string ssm_operand_shape(const wsmc_operand& a, const wsmc_operand& 
     }
     return "";
 }
+static std::string ssm_dist_shape(const wsmc_dist& a, const wsmc_dist& b, const std::string& name) {
+    if (a.family != b.family) return name + ".family";
+    if (a.mean_fn != b.mean_fn) return name + ".mean_fn";
+    if (a.dim != b.dim) return name + ".dim";
+    for (int k = 0; k < 4; ++k) {
+        const std::string w = ssm_operand_shape(a.mu[k], b.mu[k]);
+        if (!w.empty()) return name + ".mu[" + std::to_string(k) + "]." + w;
+    }
+    const std::string w = ssm_operand_shape(a.scale, b.scale);
+    if (!w.empty()) return name + ".scale." + w;
+    return "";
+}
 static std::string ssm_stmt_shape(const wsmc_ssm_stmt& a, const wsmc_ssm_stmt& b) {
     if (a.kind != b.kind) return "kind";
     if (a.col != b.col) return "col";
-    if (a.kind == WSMC_SSM_SAMPLE || a.kind == WSMC_SSM_OBSERVE) {
-        if (a.dist.family != b.dist.family) return "dist.family";
-        if (a.dist.mean_fn != b.dist.mean_fn) return "dist.mean_fn";
-        if (a.dist.dim != b.dist.dim) return "dist.dim";
-        for (int k = 0; k < 4; ++k) {
-            const std::string w = ssm_operand_shape(a.dist.mu[k], b.dist.mu[k]);
-            if (!w.empty()) return "dist.mu[" + std::to_string(k) + "]." + w;
-        }
-        const std::string w = ssm_operand_shape(a.dist.scale, b.dist.scale);
-        if (!w.empty()) return "dist.scale." + w;
+    if (ssm_is_sample(a.kind) || ssm_is_weigh(a.kind)) {
+        const std::string w = ssm_dist_shape(a.dist, b.dist, "dist");
+        if (!w.empty()) return w;
     }
-    if (a.kind == WSMC_SSM_ASSIGN || a.kind == WSMC_SSM_OBSERVE) {
+    if (a.kind == WSMC_SSM_SAMPLE_IMPORTANCE) {
+        const std::string w = ssm_dist_shape(a.target, b.target, "target");
+        if (!w.empty()) return w;
+    }
+    if (a.kind == WSMC_SSM_ASSIGN || ssm_is_weigh(a.kind)) {
         const std::string w = ssm_operand_shape(a.value, b.value);
         if (!w.empty()) return "value." + w;
     }
@@ -6063,6 +6123,8 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
             ssm_dev_image(specs + b, f.init, f.step, f.ins);
         f.seed = seeds[b];
     }
+    std::vector<SsmTarget> targ(sh.guided ? (size_t)B * kSsmTargets : 0);   // a guided spec: filter b's targets
+    for (size_t b = 0; b * kSsmTargets < targ.size(); ++b) ssm_dev_targets(specs + (n_specs == 1 ? 0 : b), targ.data() + b * kSsmTargets);
     // one allocation for the call: the state between segments ([B] rows of what a context keeps:
     // zero columns, zero log-weights and a zero ancestors row are what wsmc_create and
     // wsmc_col_create leave), the records, the images, the tables, the trace
@@ -6070,21 +6132,21 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
     const size_t nx = up(sizeof(double) * (size_t)B * S * n), nw = up(sizeof(double) * (size_t)B * n),
                  nanc = up(sizeof(int32_t) * (size_t)B * n), nrec = up(sizeof(SsmBatchRec) * (size_t)B),
                  nfilt = up(sizeof(SsmBatchFilter) * (size_t)B), ndata = up(sizeof(double) * (size_t)n_tables * T * dd),
+                 ntarg = sh.guided ? up(sizeof(SsmTarget) * kSsmTargets * (size_t)B) : 0,
                  ntrace = out->ess_trace || tr.ess ? up(sizeof(double) * (size_t)B * T) : 0,
                  nmean = tr.mean ? up(sizeof(double) * (size_t)B * T * S) : 0, nvar = tr.var ? up(sizeof(double) * (size_t)B * T * S) : 0,
                  nle = tr.log_evidence ? up(sizeof(double) * (size_t)B * T) : 0;
     const size_t nstate = nx + nw + nanc + nrec;
     const bool smooth = sm.paths || sm.mean || sm.var;
-    const int n_obs = sh.n_obs;
-    const size_t nsmooth = smooth ? ssm_smooth_carve(nullptr, sm, B, T, n, S, n_obs, nullptr) : 0;
+    const size_t nsmooth = smooth ? ssm_smooth_carve(nullptr, sm, B, T, n, sh, nullptr) : 0;
     SsmSlab slab;
     SsmSmoothClock sm_clock;
     if (smooth) {
-        if (int rc = ssm_smooth_alloc(&slab, nstate + nfilt + ndata + ntrace + nmean + nvar + nle + nsmooth + 256, "ssm smoothed batch"))
+        if (int rc = ssm_smooth_alloc(&slab, nstate + nfilt + ndata + ntarg + ntrace + nmean + nvar + nle + nsmooth + 256, "ssm smoothed batch"))
             return rc;
         WSMC_HIP(sm_clock.start());
     } else {
-        WSMC_HIP(hipMalloc(&slab.p, nstate + nfilt + ndata + ntrace + nmean + nvar + nle + 256));
+        WSMC_HIP(hipMalloc(&slab.p, nstate + nfilt + ndata + ntarg + ntrace + nmean + nvar + nle + 256));
     }
     char* q = slab.p;
     double* d_x = reinterpret_cast<double*>(q); q += nx;
@@ -6093,6 +6155,7 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
     SsmBatchRec* d_rec = reinterpret_cast<SsmBatchRec*>(q); q += nrec;
     SsmBatchFilter* d_filt = reinterpret_cast<SsmBatchFilter*>(q); q += nfilt;
     double* d_data = reinterpret_cast<double*>(q); q += ndata;
+    SsmTarget* d_targ = ntarg ? reinterpret_cast<SsmTarget*>(q) : nullptr; q += ntarg;
     double* d_trace = ntrace ? reinterpret_cast<double*>(q) : nullptr; q += ntrace;
     double* d_mean = nmean ? reinterpret_cast<double*>(q) : nullptr; q += nmean;
     double* d_var = nvar ? reinterpret_cast<double*>(q) : nullptr; q += nvar;
@@ -6100,7 +6163,7 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
     SsmSmoothBufs sb;
     std::memset(&sb, 0, sizeof(sb));
     if (smooth) {
-        ssm_smooth_carve(q, sm, B, T, n, S, n_obs, &sb);
+        ssm_smooth_carve(q, sm, B, T, n, sh, &sb);
         sb.flags_off += (size_t)(q - slab.p);
     }
     for (int32_t b = 0; b < B; ++b)
@@ -6113,13 +6176,17 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
         if (e == hipSuccess) e = hipMemcpyAsync(d_filt, filt.data(), sizeof(SsmBatchFilter) * (size_t)B, hipMemcpyHostToDevice, st);
         if (e == hipSuccess && dd > 0)
             e = hipMemcpyAsync(d_data, data, sizeof(double) * (size_t)n_tables * T * dd, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && d_targ)
+            e = hipMemcpyAsync(d_targ, targ.data(), sizeof(SsmTarget) * targ.size(), hipMemcpyHostToDevice, st);
         return e;
     };
     hipError_t e = run();
-    SsmBatchRecArgs kra;   // (a smoothed batch's launches: the same arguments and the log)
-    std::memset(&kra, 0, sizeof(kra));
+    SsmBatchGuidedArgs kga;   // (a smoothed batch's launches: the same arguments and the log; a guided spec's: and its targets)
+    std::memset(&kga, 0, sizeof(kga));
+    SsmBatchRecArgs& kra = kga.ra;
     SsmBatchArgs& ka = kra.a;
     kra.r = sb.rec;
+    kga.targ = d_targ;
     ka.x = d_x;
     ka.w = d_w;
     ka.anc = d_anc;
@@ -6129,14 +6196,14 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
     ka.tr_logev = d_le;
     ka.rec = d_rec;
     ka.filt = d_filt;
-    const int threads = ssm_threads(feat, n);
+    const int threads = sh.guided ? ssm_guided_threads(feat, n) : ssm_threads(feat, n);
     ssm_fill_args(ka, sh, n, threads, scheme, ess_min);
     ka.T = T;
     ka.B = B;
     // steps a launch: the single run's, divided by the rounds of resident workgroups the batch
     // takes, so a launch stays near the single run's 25 ms whatever B is
     int per_cu = 0, cus = 0;
-    if (e == hipSuccess) e = ssm_batch_occupancy(c->device, feat, smooth ? 2 : (d_mean || d_var || d_le) ? 1 : 0, threads, ssm_lds_bytes(n, S), &per_cu, &cus);
+    if (e == hipSuccess) e = ssm_batch_occupancy(c->device, feat, sh.guided ? (smooth ? 4 : 3) : smooth ? 2 : (d_mean || d_var || d_le) ? 1 : 0, threads, ssm_lds_bytes(n, S), &per_cu, &cus);
     if (e == hipSuccess && (per_cu < 1 || cus < 1)) e = hipErrorInvalidValue;
     int64_t nseg = 0;
     if (e == hipSuccess) {
@@ -6148,7 +6215,9 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
         for (int32_t t0 = 0; t0 < T && e == hipSuccess; t0 += K, ++nseg) {
             set_segment(ka, t0, K, T);
             ka.last = t0 + ka.nsteps == T;
-            e = smooth ? launch_ssm_batch_segment_rec(st, kra, feat, threads) : launch_ssm_batch_segment(st, ka, feat, threads);
+            e = sh.guided ? launch_ssm_batch_guided_segment(st, kga, feat, threads, smooth)
+                : smooth  ? launch_ssm_batch_segment_rec(st, kra, feat, threads)
+                          : launch_ssm_batch_segment(st, ka, feat, threads);
         }
     }
     if (e == hipSuccess) e = sm_clock.mark(1, st);

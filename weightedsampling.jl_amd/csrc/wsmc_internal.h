@@ -386,6 +386,8 @@ struct wsmc_ctx {
     int64_t ssm_book_us = 0, ssm_wall_us = 0;
     double* ssm_rows = nullptr;             // [ssm_rows_cap] a traced run's rows: means, variances, evidence (wsmc_ssm_run_traced)
     int64_t ssm_rows_cap = 0;
+    double* ssm_targets = nullptr;          // a guided run's targets (SsmTarget[kSsmTargets]), read by its kernels
+    int64_t ssm_targets_cap = 0;
     // wsmc_ssm_run_batch (it touches nothing else of the context): steps per launch (0: the
     // default), then the last call's resident blocks per CU, CU count, segments and wall time
     int32_t ssm_batch_segment = 0;
@@ -973,15 +975,18 @@ struct SsmArgs {
 };
 static_assert(sizeof(SsmArgs) + 32 <= 4096, "the spec rides in the kernel arguments");
 // A smoothed run (wsmc_ssm_run_smoothed, csrc/wsmc_ssm_smooth.hip): what the recording kernels log
-// to device memory. hist: the columns at every trace point; alog: one slot per (step, OBSERVE of
-// the step) for the ancestors of the Resample that follows the OBSERVE, written when it ran, with
-// the slot's flag in `ran` (zeroed before the run), so nothing is carried across launches. A
-// Resample after a SAMPLE never runs and has no slot. A batch's filter b has its own [T] rows.
+// to device memory. hist: the columns at every trace point; alog: one slot per (step, Resample of
+// the step that can run: the one after an OBSERVE, a WEIGHT or an importance SAMPLE) for that
+// Resample's ancestors, written when it ran, with the slot's flag in `ran` (zeroed before the
+// run), so nothing is carried across launches. A Resample after a plain SAMPLE never runs and has
+// no slot. The trace point lies before the Resample of slot trace_slot, the last OBSERVE's: in a
+// spec of SAMPLE / ASSIGN / OBSERVE alone the step's last slot. A batch's filter b has its own [T] rows.
 struct SsmRec {
     double* hist;             // [B][T][S][N]
-    int32_t* alog;            // [B][T * n_obs][N]
-    int32_t* ran;             // [B][T * n_obs]
-    int32_t n_obs, T;         // OBSERVEs a step; the run's steps (a filter's stride)
+    int32_t* alog;            // [B][T * n_slots][N]
+    int32_t* ran;             // [B][T * n_slots]
+    int32_t n_slots, T;       // slots a step; the run's steps (a filter's stride)
+    int32_t trace_slot, pad;  // the slot of the step's last OBSERVE
 };
 // the recording kernel's arguments: the run's own, unchanged and first, so that the kernels of the
 // untraced and traced units keep their argument layout
@@ -990,9 +995,30 @@ struct SsmRecArgs {
     SsmRec r;
 };
 static_assert(sizeof(SsmRecArgs) + 32 <= 4096, "the spec rides in the kernel arguments");
+// A guided spec (one with an importance SAMPLE or a WEIGHT) runs on kernels of its own
+// (csrc/wsmc_ssm_guided.hip and its recording and batch twins), so that every other spec launches
+// what it always has. SsmStmt does not grow: the kernel arguments have no room for twelve more
+// dists, so an importance Sample's target is read from device memory at a block-uniform address,
+// statement q of `init` at [q], of `step` at [WSMC_SSM_MAX_INIT + q] ([B] such rows for a batch).
+struct SsmTarget {
+    int32_t family, pad;
+    wsmc_operand mu, scale;
+    double param[2];
+};
+constexpr int kSsmTargets = WSMC_SSM_MAX_INIT + WSMC_SSM_MAX_STMTS;
+struct SsmGuidedArgs {        // both guided single-run kernels (r: the recording one's log)
+    SsmRecArgs ra;
+    const SsmTarget* targ;    // [kSsmTargets]
+};
+static_assert(sizeof(SsmGuidedArgs) + 32 <= 4096, "the spec rides in the kernel arguments");
 size_t ssm_lds_bytes(int n, int S);
 // feat: WSMC_FEAT_EXT / WSMC_FEAT_GAM bits over the spec's dists (the kernel's instantiation)
 int ssm_threads(unsigned feat, int n);
+// the guided kernels' (their log-Gamma variant has a smaller launch bound: more particles a thread)
+int ssm_guided_threads(unsigned feat, int n);
+// a guided spec's segment: the traced-capable guided instantiation (its tr_ pointers may all be
+// null), the recording one when rec is set
+hipError_t launch_ssm_guided_segment(hipStream_t s, const SsmGuidedArgs& a, unsigned feat, int threads, bool rec);
 // (the traced instantiation when a tr_ pointer is set, else the one an untraced run has always had)
 hipError_t launch_ssm_segment(hipStream_t s, const SsmArgs& a, unsigned feat, int threads);
 // the recording instantiation (always a traced one: its tr_ pointers may all be null)
@@ -1000,7 +1026,7 @@ hipError_t launch_ssm_segment_rec(hipStream_t s, const SsmRecArgs& a, unsigned f
 // After the run's last segment (csrc/wsmc_ssm_smooth.hip), for B filters of T steps:
 // launch_ssm_traceback follows every final particle back through the log, one workgroup a filter,
 // and leaves idx_t (final particle i's ancestor at trace point t) in place over slot
-// (t, n_obs - 1); launch_ssm_smooth_rows, one workgroup a (filter, step), gathers row t of hist
+// (t, trace_slot); launch_ssm_smooth_rows, one workgroup a (filter, step), gathers row t of hist
 // through idx_t in place and takes wsmc_weighted_moments of it under the final weights w [B][N]
 // (ss_trace_row's canonical sums). mean / var: [B][T][S], null: not wanted; paths: whether hist
 // is read afterwards (without it the gathered row is not written back).
@@ -1049,11 +1075,16 @@ struct SsmBatchRecArgs {      // the recording batch kernel's arguments (see Ssm
     SsmBatchArgs a;
     SsmRec r;
 };
+struct SsmBatchGuidedArgs {   // both guided batch kernels (see SsmGuidedArgs)
+    SsmBatchRecArgs ra;
+    const SsmTarget* targ;    // [B][kSsmTargets]
+};
 // blocks of the variant that are resident on one CU (by registers, waves and LDS), and the device's CUs.
-// variant: 0 untraced, 1 traced, 2 recording
+// variant: 0 untraced, 1 traced, 2 recording, 3 guided, 4 guided recording
 hipError_t ssm_batch_occupancy(int device, unsigned feat, int variant, int threads, size_t lds, int* per_cu, int* cus);
 hipError_t launch_ssm_batch_segment(hipStream_t s, const SsmBatchArgs& a, unsigned feat, int threads);
 hipError_t launch_ssm_batch_segment_rec(hipStream_t s, const SsmBatchRecArgs& a, unsigned feat, int threads);
+hipError_t launch_ssm_batch_guided_segment(hipStream_t s, const SsmBatchGuidedArgs& a, unsigned feat, int threads, bool rec);
 // one handle over several devices (wsmc_multi.hip): the ABI entry points fan out
 int multi_destroy(wsmc_ctx* c);
 wsmc_ctx* multi_first(wsmc_ctx* c);

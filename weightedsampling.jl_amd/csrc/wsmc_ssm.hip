@@ -35,7 +35,27 @@ namespace wsmc {
 // smoothed run: traced instantiations that also log the trace point's columns and each Resample's
 // ancestors (SsmRec). They are a kernel of another name with arguments of their own, so the other
 // two units' kernels are, to the instruction, what they were before there was a log.
+// A fourth and a fifth time through csrc/wsmc_ssm_guided.hip (WSMC_SSM_GUIDED) and
+// csrc/wsmc_ssm_guided_smooth.hip (both macros) for the kernels of a guided spec, one with an
+// importance SAMPLE or a WEIGHT: traced-capable instantiations (null trace pointers serve an
+// untraced call) whose statement body also holds k_sample_importance's arithmetic, and their
+// recording twins. Kernels of other names again, so a spec without the new kinds launches what it
+// always has.
+#if defined(WSMC_SSM_GUIDED)
+constexpr bool kSsTraced = true, kSsGuided = true;
 #if defined(WSMC_SSM_SMOOTH)
+#define WSMC_SSM_VARIANTS ssm_launch_guided_rec
+#define WSMC_SSM_KERNEL k_ssm_guided_segment_rec
+#else
+#define WSMC_SSM_VARIANTS ssm_launch_guided
+#define WSMC_SSM_KERNEL k_ssm_guided_segment
+#endif
+typedef SsmGuidedArgs SsKernArgs;
+namespace {
+constexpr int kSsVariantGamThreads = kSsGuidedGamThreads;
+typedef const SsmTarget __attribute__((address_space(4))) * SsTargetPtr;
+}
+#elif defined(WSMC_SSM_SMOOTH)
 constexpr bool kSsTraced = true;
 #define WSMC_SSM_VARIANTS ssm_launch_rec
 #define WSMC_SSM_KERNEL k_ssm_segment_rec
@@ -57,6 +77,13 @@ size_t ssm_lds_bytes(int n, int S) {
 }
 #endif
 
+#ifndef WSMC_SSM_GUIDED
+namespace {
+constexpr bool kSsGuided = false;
+constexpr int kSsVariantGamThreads = kSsGamThreads;
+}
+#endif
+
 // TR: the traced run (wsmc_ssm_run_traced), which also leaves row t of the moments and the evidence
 // at the ESS trace's point
 template <unsigned FEAT, int THREADS, bool TR>
@@ -65,6 +92,13 @@ __global__ __launch_bounds__(THREADS) void WSMC_SSM_KERNEL(SsKernArgs) {
 #ifdef WSMC_SSM_SMOOTH
     static_assert(offsetof(SsmRecArgs, a) == 0, "the run's arguments come first");
     const SsmRec& rc = *(const SsmRec*)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(SsmRecArgs, r));
+#endif
+#ifdef WSMC_SSM_GUIDED
+    static_assert(offsetof(SsmGuidedArgs, ra) == 0, "the run's arguments come first");
+    // the targets: written before the run's first launch and by nothing while a kernel runs; a
+    // uniform address, so the loads are scalar (as the batch kernel reads its SsmBatchFilter)
+    const SsmTarget* const tgs = (const SsmTarget*)(SsTargetPtr)(
+        *(const SsmTarget* const*)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(SsmGuidedArgs, targ)));
 #endif
     extern __shared__ __attribute__((aligned(16))) char ss_smem[];
     const int tid = (int)threadIdx.x, nthr = (int)blockDim.x;
@@ -120,14 +154,20 @@ __global__ __launch_bounds__(THREADS) void WSMC_SSM_KERNEL(SsKernArgs) {
             if (s + 1 < a.nsteps) dnext = ss_row(data, dd, t + 1);   // in flight during this step
         }
 #ifdef WSMC_SSM_SMOOTH
-        int slot = t * rc.n_obs;   // the log's slot of the step's next OBSERVE
+        int slot = t * rc.n_slots;   // the log's slot of the step's next Resample that can run
 #endif
         for (int q = 0; q < nst; ++q) {
             const SsmStmt& st = list[q];
+#ifdef WSMC_SSM_GUIDED
+            ss_statement<FEAT, true>(st, a.ins, L, dv, a.seed, op, tgs + (init ? q : WSMC_SSM_MAX_INIT + q));
+#else
             ss_statement<FEAT>(st, a.ins, L, dv, a.seed, op);
+#endif
             if (st.kind == WSMC_SSM_SAMPLE) {
                 op += 2;   // the draws, then a Resample that does not run (the weights have not changed)
-            } else if (st.kind == WSMC_SSM_OBSERVE) {
+            } else if (st.kind == WSMC_SSM_OBSERVE ||
+                       (kSsGuided && (st.kind == WSMC_SSM_WEIGHT || st.kind == WSMC_SSM_SAMPLE_IMPORTANCE))) {
+                if (kSsGuided && st.kind == WSMC_SSM_SAMPLE_IMPORTANCE) op += 1;   // its draws took `op`; its Resample can run
                 const bool row = TR && !init && q == a.last_obs;
 #ifdef WSMC_SSM_SMOOTH
                 if (row) ss_record_cols(L, rc.hist + (size_t)t * S * N);
@@ -175,15 +215,19 @@ static hipError_t ssm_launch(hipStream_t s, const SsKernArgs& a, int threads, si
 }
 // this unit's three feature variants (launch_ssm_segment has checked the arguments)
 hipError_t WSMC_SSM_VARIANTS(hipStream_t s, const SsKernArgs& a, unsigned feat, int threads, size_t lds) {
-    if (feat & WSMC_FEAT_GAM) return ssm_launch<kSsFeatGam, kSsGamThreads>(s, a, threads, lds);
+    if (feat & WSMC_FEAT_GAM) return ssm_launch<kSsFeatGam, kSsVariantGamThreads>(s, a, threads, lds);
     if (feat & WSMC_FEAT_EXT) return ssm_launch<kSsFeatExt, kSsMaxThreads>(s, a, threads, lds);
     return ssm_launch<0u, kSsMaxThreads>(s, a, threads, lds);
 }
 
-#if !defined(WSMC_SSM_TRACED) && !defined(WSMC_SSM_SMOOTH)
+#if !defined(WSMC_SSM_TRACED) && !defined(WSMC_SSM_SMOOTH) && !defined(WSMC_SSM_GUIDED)
 int ssm_threads(unsigned feat, int n) {
     const int cap = (feat & WSMC_FEAT_GAM) ? kSsGamThreads : kSsMaxThreads;
     // two particles a thread where the workgroup allows (wsmc_lgssm1d_run's measured choice)
+    return std::max(64, std::min(cap, ((n + 127) / 128) * 64));
+}
+int ssm_guided_threads(unsigned feat, int n) {
+    const int cap = (feat & WSMC_FEAT_GAM) ? kSsGuidedGamThreads : kSsMaxThreads;
     return std::max(64, std::min(cap, ((n + 127) / 128) * 64));
 }
 
@@ -199,10 +243,24 @@ hipError_t launch_ssm_segment(hipStream_t s, const SsmArgs& a, unsigned feat, in
 }
 
 hipError_t launch_ssm_segment_rec(hipStream_t s, const SsmRecArgs& a, unsigned feat, int threads) {
-    if (!ss_segment_ok(a.a, feat, threads) || !a.r.hist || !a.r.alog || !a.r.ran || a.r.n_obs < 1 ||
+    if (!ss_segment_ok(a.a, feat, threads) || !a.r.hist || !a.r.alog || !a.r.ran || a.r.n_slots < 1 ||
         a.a.t0 + a.a.nsteps > a.r.T)
         return hipErrorInvalidValue;
     return ssm_launch_rec(s, a, feat, threads, ssm_lds_bytes(a.a.N, a.a.S));
+}
+
+hipError_t ssm_launch_guided(hipStream_t s, const SsmGuidedArgs& a, unsigned feat, int threads, size_t lds);       // csrc/wsmc_ssm_guided.hip
+hipError_t ssm_launch_guided_rec(hipStream_t s, const SsmGuidedArgs& a, unsigned feat, int threads, size_t lds);   // csrc/wsmc_ssm_guided_smooth.hip
+
+hipError_t launch_ssm_guided_segment(hipStream_t s, const SsmGuidedArgs& a, unsigned feat, int threads, bool rec) {
+    const SsmArgs& ra = a.ra.a;
+    const SsmRec& r = a.ra.r;
+    if (!ss_segment_ok(ra, feat, threads, true) || !a.targ) return hipErrorInvalidValue;
+    if (rec && (!r.hist || !r.alog || !r.ran || r.n_slots < 1 || r.trace_slot < 0 || r.trace_slot >= r.n_slots ||
+                ra.t0 + ra.nsteps > r.T))
+        return hipErrorInvalidValue;
+    const size_t lds = ssm_lds_bytes(ra.N, ra.S);
+    return rec ? ssm_launch_guided_rec(s, a, feat, threads, lds) : ssm_launch_guided(s, a, feat, threads, lds);
 }
 #endif
 

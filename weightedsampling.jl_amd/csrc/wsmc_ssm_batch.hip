@@ -25,7 +25,26 @@ namespace wsmc {
 // csrc/wsmc_ssm_batch_traced.hip (WSMC_SSM_TRACED) for the traced ones
 // and through csrc/wsmc_ssm_batch_smooth.hip (WSMC_SSM_SMOOTH) for the recording ones of a smoothed
 // batch: a kernel of another name with arguments of its own, as in csrc/wsmc_ssm.hip
+// and through csrc/wsmc_ssm_batch_guided.hip (WSMC_SSM_GUIDED) and
+// csrc/wsmc_ssm_batch_guided_smooth.hip (both macros) for the kernels of a guided spec's batch, as
+// in csrc/wsmc_ssm.hip
+#if defined(WSMC_SSM_GUIDED)
+constexpr bool kSsbTraced = true, kSsbGuided = true;
 #if defined(WSMC_SSM_SMOOTH)
+#define WSMC_SSB_OCCUPANCY ssb_occupancy_guided_rec
+#define WSMC_SSB_VARIANTS ssb_launch_guided_rec
+#define WSMC_SSB_KERNEL k_ssm_batch_guided_segment_rec
+#else
+#define WSMC_SSB_OCCUPANCY ssb_occupancy_guided
+#define WSMC_SSB_VARIANTS ssb_launch_guided
+#define WSMC_SSB_KERNEL k_ssm_batch_guided_segment
+#endif
+typedef SsmBatchGuidedArgs SsbKernArgs;
+namespace {
+constexpr int kSsbVariantGamThreads = kSsGuidedGamThreads;
+typedef const SsmTarget __attribute__((address_space(4))) * SsTargetPtr;
+}
+#elif defined(WSMC_SSM_SMOOTH)
 constexpr bool kSsbTraced = true;
 #define WSMC_SSB_OCCUPANCY ssb_occupancy_rec
 #define WSMC_SSB_VARIANTS ssb_launch_rec
@@ -47,11 +66,19 @@ typedef SsmBatchArgs SsbKernArgs;
 
 namespace {
 typedef const SsmBatchFilter __attribute__((address_space(4))) * SsFilterPtr;
+#ifndef WSMC_SSM_GUIDED
+constexpr bool kSsbGuided = false;
+constexpr int kSsbVariantGamThreads = kSsGamThreads;
+#endif
 }
 
 // TR: the traced batch (wsmc_ssm_run_batch_traced), k_ssm_segment's flag
 template <unsigned FEAT, int THREADS, bool TR>
-#ifdef WSMC_SSM_SMOOTH
+#if defined(WSMC_SSM_GUIDED)
+__global__ __launch_bounds__(THREADS) void WSMC_SSB_KERNEL(const SsmBatchGuidedArgs ga) {
+    const SsmBatchRecArgs& ka = ga.ra;
+    const SsmBatchArgs& a = ka.a;
+#elif defined(WSMC_SSM_SMOOTH)
 __global__ __launch_bounds__(THREADS) void WSMC_SSB_KERNEL(const SsmBatchRecArgs ka) {
     const SsmBatchArgs& a = ka.a;
 #else
@@ -63,8 +90,12 @@ __global__ __launch_bounds__(THREADS) void WSMC_SSB_KERNEL(const SsmBatchArgs a)
 #ifdef WSMC_SSM_SMOOTH
     // filter b's rows of the history and of the log
     double* hist = ka.r.hist + b * (size_t)ka.r.T * (size_t)a.S * (size_t)a.N;
-    int32_t* alog = ka.r.alog + b * (size_t)ka.r.T * (size_t)ka.r.n_obs * (size_t)a.N;
-    int32_t* ranf = ka.r.ran + b * (size_t)ka.r.T * (size_t)ka.r.n_obs;
+    int32_t* alog = ka.r.alog + b * (size_t)ka.r.T * (size_t)ka.r.n_slots * (size_t)a.N;
+    int32_t* ranf = ka.r.ran + b * (size_t)ka.r.T * (size_t)ka.r.n_slots;
+#endif
+#ifdef WSMC_SSM_GUIDED
+    // filter b's targets (block-uniform: scalar loads, as its statements' below)
+    const SsmTarget* const tgs = (const SsmTarget*)((SsTargetPtr)ga.targ + b * (size_t)kSsmTargets);
 #endif
     const SsmBatchFilter& f = *(const SsmBatchFilter*)((SsFilterPtr)a.filt + b);
     const int N = a.N, P = a.P, S = a.S;
@@ -124,14 +155,20 @@ __global__ __launch_bounds__(THREADS) void WSMC_SSB_KERNEL(const SsmBatchArgs a)
             if (s + 1 < a.nsteps) dnext = ss_row(data, dd, t + 1);   // in flight during this step
         }
 #ifdef WSMC_SSM_SMOOTH
-        int slot = t * ka.r.n_obs;   // the log's slot of the step's next OBSERVE
+        int slot = t * ka.r.n_slots;   // the log's slot of the step's next Resample that can run
 #endif
         for (int q = 0; q < nst; ++q) {
             const SsmStmt& st = list[q];
+#ifdef WSMC_SSM_GUIDED
+            ss_statement<FEAT, true>(st, f.ins, L, dv, seed, op, tgs + (init ? q : WSMC_SSM_MAX_INIT + q));
+#else
             ss_statement<FEAT>(st, f.ins, L, dv, seed, op);
+#endif
             if (st.kind == WSMC_SSM_SAMPLE) {
                 op += 2;   // the draws, then a Resample that does not run (the weights have not changed)
-            } else if (st.kind == WSMC_SSM_OBSERVE) {
+            } else if (st.kind == WSMC_SSM_OBSERVE ||
+                       (kSsbGuided && (st.kind == WSMC_SSM_WEIGHT || st.kind == WSMC_SSM_SAMPLE_IMPORTANCE))) {
+                if (kSsbGuided && st.kind == WSMC_SSM_SAMPLE_IMPORTANCE) op += 1;   // its draws took `op`; its Resample can run
                 const bool row = TR && !init && q == a.last_obs;
                 const size_t r = b * (size_t)a.T + (size_t)t;
 #ifdef WSMC_SSM_SMOOTH
@@ -238,17 +275,21 @@ hipError_t ssb_launch(hipStream_t s, const SsbKernArgs& a, int threads, size_t l
 
 // this unit's three feature variants
 hipError_t WSMC_SSB_OCCUPANCY(unsigned feat, int threads, size_t lds, int* per_cu) {
-    if (feat & WSMC_FEAT_GAM) return ssb_occupancy<kSsFeatGam, kSsGamThreads>(threads, lds, per_cu);
+    if (feat & WSMC_FEAT_GAM) return ssb_occupancy<kSsFeatGam, kSsbVariantGamThreads>(threads, lds, per_cu);
     if (feat & WSMC_FEAT_EXT) return ssb_occupancy<kSsFeatExt, kSsMaxThreads>(threads, lds, per_cu);
     return ssb_occupancy<0u, kSsMaxThreads>(threads, lds, per_cu);
 }
 hipError_t WSMC_SSB_VARIANTS(hipStream_t s, const SsbKernArgs& a, unsigned feat, int threads, size_t lds, int B) {
-    if (feat & WSMC_FEAT_GAM) return ssb_launch<kSsFeatGam, kSsGamThreads>(s, a, threads, lds, B);
+    if (feat & WSMC_FEAT_GAM) return ssb_launch<kSsFeatGam, kSsbVariantGamThreads>(s, a, threads, lds, B);
     if (feat & WSMC_FEAT_EXT) return ssb_launch<kSsFeatExt, kSsMaxThreads>(s, a, threads, lds, B);
     return ssb_launch<0u, kSsMaxThreads>(s, a, threads, lds, B);
 }
 
-#if !defined(WSMC_SSM_TRACED) && !defined(WSMC_SSM_SMOOTH)
+#if !defined(WSMC_SSM_TRACED) && !defined(WSMC_SSM_SMOOTH) && !defined(WSMC_SSM_GUIDED)
+hipError_t ssb_occupancy_guided(unsigned feat, int threads, size_t lds, int* per_cu);       // csrc/wsmc_ssm_batch_guided.hip
+hipError_t ssb_launch_guided(hipStream_t s, const SsmBatchGuidedArgs& a, unsigned feat, int threads, size_t lds, int B);
+hipError_t ssb_occupancy_guided_rec(unsigned feat, int threads, size_t lds, int* per_cu);   // csrc/wsmc_ssm_batch_guided_smooth.hip
+hipError_t ssb_launch_guided_rec(hipStream_t s, const SsmBatchGuidedArgs& a, unsigned feat, int threads, size_t lds, int B);
 hipError_t ssb_occupancy_traced(unsigned feat, int threads, size_t lds, int* per_cu);   // csrc/wsmc_ssm_batch_traced.hip
 hipError_t ssb_launch_traced(hipStream_t s, const SsmBatchArgs& a, unsigned feat, int threads, size_t lds, int B);
 hipError_t ssb_occupancy_rec(unsigned feat, int threads, size_t lds, int* per_cu);      // csrc/wsmc_ssm_batch_smooth.hip
@@ -257,12 +298,14 @@ hipError_t ssb_launch_rec(hipStream_t s, const SsmBatchRecArgs& a, unsigned feat
 hipError_t ssm_batch_occupancy(int device, unsigned feat, int variant, int threads, size_t lds, int* per_cu, int* cus) {
     const hipError_t e = hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, device);
     if (e != hipSuccess) return e;
+    if (variant == 4) return ssb_occupancy_guided_rec(feat, threads, lds, per_cu);
+    if (variant == 3) return ssb_occupancy_guided(feat, threads, lds, per_cu);
     if (variant == 2) return ssb_occupancy_rec(feat, threads, lds, per_cu);
     return variant ? ssb_occupancy_traced(feat, threads, lds, per_cu) : ssb_occupancy_untraced(feat, threads, lds, per_cu);
 }
 
-static bool ssb_segment_ok(const SsmBatchArgs& a, unsigned feat, int threads) {
-    return ss_segment_ok(a, feat, threads) && a.B >= 1 && a.t0 + a.nsteps <= a.T && a.x && a.w && a.anc && a.rec && a.filt;
+static bool ssb_segment_ok(const SsmBatchArgs& a, unsigned feat, int threads, bool guided = false) {
+    return ss_segment_ok(a, feat, threads, guided) && a.B >= 1 && a.t0 + a.nsteps <= a.T && a.x && a.w && a.anc && a.rec && a.filt;
 }
 
 hipError_t launch_ssm_batch_segment(hipStream_t s, const SsmBatchArgs& a, unsigned feat, int threads) {
@@ -273,9 +316,19 @@ hipError_t launch_ssm_batch_segment(hipStream_t s, const SsmBatchArgs& a, unsign
 }
 
 hipError_t launch_ssm_batch_segment_rec(hipStream_t s, const SsmBatchRecArgs& a, unsigned feat, int threads) {
-    if (!ssb_segment_ok(a.a, feat, threads) || !a.r.hist || !a.r.alog || !a.r.ran || a.r.n_obs < 1 || a.r.T != a.a.T)
+    if (!ssb_segment_ok(a.a, feat, threads) || !a.r.hist || !a.r.alog || !a.r.ran || a.r.n_slots < 1 || a.r.T != a.a.T)
         return hipErrorInvalidValue;
     return ssb_launch_rec(s, a, feat, threads, ssm_lds_bytes(a.a.N, a.a.S), a.a.B);
+}
+
+hipError_t launch_ssm_batch_guided_segment(hipStream_t s, const SsmBatchGuidedArgs& a, unsigned feat, int threads, bool rec) {
+    const SsmBatchArgs& ba = a.ra.a;
+    const SsmRec& r = a.ra.r;
+    if (!ssb_segment_ok(ba, feat, threads, true) || !a.targ) return hipErrorInvalidValue;
+    if (rec && (!r.hist || !r.alog || !r.ran || r.n_slots < 1 || r.trace_slot < 0 || r.trace_slot >= r.n_slots || r.T != ba.T))
+        return hipErrorInvalidValue;
+    const size_t lds = ssm_lds_bytes(ba.N, ba.S);
+    return rec ? ssb_launch_guided_rec(s, a, feat, threads, lds, ba.B) : ssb_launch_guided(s, a, feat, threads, lds, ba.B);
 }
 #endif
 

@@ -114,8 +114,10 @@ __device__ inline double ss_eval(const SsOp& r, const double* cb, int i) {
     if (r.o1 >= 0) v = v + r.k1 * cb[r.o1 + i];
     return v;
 }
-// the statement's dist with its two parameters evaluated for one particle
-__device__ inline void ss_dist(wsmc_dist* d, const SsmStmt& st, double m, double s) {
+// the statement's dist (Src: SsmStmt), or an importance Sample's target (SsmTarget), with its two
+// parameters evaluated for one particle
+template <class Src>
+__device__ inline void ss_dist(wsmc_dist* d, const Src& st, double m, double s) {
     d->family = st.family;
     d->mean_fn = WSMC_MEAN_AFFINE;
     d->dim = 1;
@@ -128,12 +130,36 @@ __device__ inline void ss_dist(wsmc_dist* d, const SsmStmt& st, double m, double
     d->param[1] = st.param[1];
 }
 
-// one statement over this thread's particles. op: the statement's op counter (a SAMPLE's draws)
-template <unsigned FEAT>
+// one statement over this thread's particles. op: the statement's op counter (a SAMPLE's draws).
+// GUIDED (the guided kernels alone): the spec may hold an importance SAMPLE, whose target is tg,
+// and a WEIGHT, which is OBSERVE's arithmetic
+template <unsigned FEAT, bool GUIDED = false>
 __device__ inline void ss_statement(const SsmStmt& st, const SsmIns* ins, SsState& L, const SsData& dv, uint64_t seed,
-                                    uint64_t op) {
+                                    uint64_t op, const SsmTarget* tg = nullptr) {
     double* cb = L.cb;
     const int kind = st.kind;
+    if constexpr (GUIDED) {
+        if (kind == WSMC_SSM_SAMPLE_IMPORTANCE) {   // k_sample_importance, a particle at a time
+            const SsOp pm = ss_resolve(st.mu, L, dv), ps = ss_resolve(st.scale, L, dv);
+            const SsOp tm = ss_resolve(tg->mu, L, dv), ts = ss_resolve(tg->scale, L, dv);
+            double* out = cb + ss_buf(L, st.col) * L.stride;
+            for (int i = L.i0; i < L.i1; ++i) {
+                wsmc_dist d;
+                ss_dist(&d, st, ss_eval(pm, cb, i), ss_eval(ps, cb, i));
+                double x[4];
+                wsmc_dist_sample_mf(&d, x, seed, op, (uint64_t)i, nullptr, L.N, i, nullptr, FEAT);
+                out[i] = x[0];
+                // both dists' operands again: one that reads the output column sees the new value
+                wsmc_dist t;
+                ss_dist(&t, *tg, ss_eval(tm, cb, i), ss_eval(ts, cb, i));
+                const double lt = wsmc_dist_logpdf_mf(&t, x, nullptr, L.N, i, nullptr, nullptr, FEAT);
+                ss_dist(&d, st, ss_eval(pm, cb, i), ss_eval(ps, cb, i));
+                const double lp = wsmc_dist_logpdf_mf(&d, x, nullptr, L.N, i, nullptr, nullptr, FEAT);
+                L.lw[i] = L.lw[i] + (lt - lp);
+            }
+            return;
+        }
+    }
     if (kind == WSMC_SSM_SAMPLE) {
         const SsOp mu = ss_resolve(st.mu, L, dv), sc = ss_resolve(st.scale, L, dv);
         double* out = cb + ss_buf(L, st.col) * L.stride;
@@ -173,7 +199,7 @@ __device__ inline void ss_statement(const SsmStmt& st, const SsmIns* ins, SsStat
             }
             out[i] = k.top;
         }
-    } else {   // OBSERVE
+    } else {   // OBSERVE (a guided kernel: or WEIGHT)
         const SsOp mu = ss_resolve(st.mu, L, dv), sc = ss_resolve(st.scale, L, dv), xv = ss_resolve(st.value, L, dv);
         wsmc_logmemo lm = {0, 0.0, 0.0, 0};   // the thread's particles often share one scale value
         for (int i = L.i0; i < L.i1; ++i) {
@@ -482,12 +508,16 @@ __device__ inline void ss_record_anc(const SsState& L, int32_t* slot, int32_t* r
 // VGPRs of a 1024-thread workgroup without a spill (DESIGN.md §4 has the listing).
 constexpr unsigned kSsFeatExt = WSMC_FEAT_EXT, kSsFeatGam = WSMC_FEAT_EXT | WSMC_FEAT_GAM;
 constexpr int kSsGamThreads = 1024;
+// the guided kernels' (an importance Sample holds a sampler and two log-densities at once): their
+// log-Gamma variant does not fit 128 VGPRs without a spill, so it runs at most 512 threads, with
+// more particles a thread at the sizes past 1024 (the caps are LDS's and do not move)
+constexpr int kSsGuidedGamThreads = 512;
 
 // ---- host side: what the launch wrappers of both files share (no kernel calls these) ----
 // a segment's arguments within the kernels' limits, for the fields SsmArgs and SsmBatchArgs share
 template <class Args>
-inline bool ss_segment_ok(const Args& a, unsigned feat, int threads) {
-    const int tmax = (feat & WSMC_FEAT_GAM) ? kSsGamThreads : kSsMaxThreads;
+inline bool ss_segment_ok(const Args& a, unsigned feat, int threads, bool guided = false) {
+    const int tmax = (feat & WSMC_FEAT_GAM) ? (guided ? kSsGuidedGamThreads : kSsGamThreads) : kSsMaxThreads;
     return !(a.S < 1 || a.S > WSMC_SSM_MAX_COLS || a.N < 1 || a.N > ssm_cap(a.S) || threads < 64 || threads > tmax ||
         (threads & 63) || (int64_t)a.P * threads < a.N || a.nsteps < 0 || a.t0 < 0 || a.data_dim < 0 ||
         a.data_dim > WSMC_SSM_MAX_DATA || a.n_init < 0 || a.n_init > WSMC_SSM_MAX_INIT || a.n_step < 1 ||

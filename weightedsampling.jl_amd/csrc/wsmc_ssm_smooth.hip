@@ -4,16 +4,17 @@
 // logged into trajectories and smoothed moments after the run's last segment.
 //
 // The log (SsmRec): row t of `hist` holds the S columns at trace point t; slot (t, j) of `alog`
-// holds the ancestors of the Resample after step t's j-th OBSERVE where `ran` says it ran. The final
-// particle i sits at index i; going back, a Resample that ran sends index idx to anc[idx]. Trace
-// point t lies before the Resample of slot (t, n_obs - 1) and after those of slots (t, 0 ..
-// n_obs - 2) and of step t - 1.
+// holds the ancestors of step t's j-th Resample that can run (after an OBSERVE, a WEIGHT or an
+// importance SAMPLE) where `ran` says it ran. The final particle i sits at index i; going back, a
+// Resample that ran sends index idx to anc[idx]. Trace point t lies before the Resample of slot
+// (t, trace_slot), the step's last OBSERVE's, and after those of slots (t, 0 .. trace_slot - 1) and
+// of step t - 1; in a spec without WEIGHT and importance SAMPLE trace_slot is the step's last slot.
 //
 // Phase 1 (k_ssm_traceback) is sequential in t: one workgroup a filter walks the slots from the
 // last to the first. The dependent chain idx -> anc[idx] would run at memory latency if it read the
 // log in place, so the workgroup stages a chunk of rows in LDS (independent, coalesced loads, all in
 // flight at once) and every thread walks its particles through the chunk at LDS latency. idx_t is
-// written over slot (t, n_obs - 1), whose row has been staged by then.
+// written over slot (t, trace_slot), whose row has been staged by then.
 // Phase 2 (k_ssm_smooth_rows) is parallel: one workgroup a (filter, step) gathers row t of the
 // history through idx_t into LDS in the fused kernel's layout, writes it back in place (the
 // paths) and calls ss_trace_row on it with the final log-weights: the canonical sums of
@@ -43,7 +44,7 @@ __global__ __launch_bounds__(kTbThreads) void k_ssm_traceback(SsmRec r, int N) {
     extern __shared__ __attribute__((aligned(16))) int32_t tb_smem[];
     const int tid = (int)threadIdx.x, nthr = (int)blockDim.x;
     const size_t b = blockIdx.x;
-    const int n_obs = r.n_obs, M = r.T * n_obs, R = tb_rows(N);
+    const int n_slots = r.n_slots, trace_slot = r.trace_slot, M = r.T * n_slots, R = tb_rows(N);
     int32_t* alog = r.alog + b * (size_t)M * (size_t)N;
     const int32_t* ran = r.ran + b * (size_t)M;
     int32_t* cur = tb_smem;                      // [N] where each final particle's ancestor sits
@@ -67,7 +68,7 @@ __global__ __launch_bounds__(kTbThreads) void k_ssm_traceback(SsmRec r, int N) {
             for (int q = cnt - 1; q >= 0; --q) {
                 if (flag[q]) idx = rows[q * N + idx];
                 const int slot = lo + q;
-                if (slot % n_obs == n_obs - 1) alog[(size_t)slot * N + i] = idx;   // idx_t
+                if (slot % n_slots == trace_slot) alog[(size_t)slot * N + i] = idx;   // idx_t
             }
             cur[i] = idx;
         }
@@ -105,7 +106,7 @@ __global__ __launch_bounds__(kSsMaxThreads) void k_ssm_smooth_rows(SsmRowsArgs a
 #ifdef WSMC_TABLES_LDS
     wsmc_tables_to_lds();   // before any exp (every thread: it ends in a barrier)
 #endif
-    const int32_t* idx = a.r.alog + (bt * a.r.n_obs + (size_t)(a.r.n_obs - 1)) * N;
+    const int32_t* idx = a.r.alog + (bt * a.r.n_slots + (size_t)a.r.trace_slot) * N;
     double* hist = a.r.hist + bt * (size_t)S * N;
     const double* w = a.w + b * (size_t)N;
     for (int i = L.i0; i < L.i1; ++i) L.lw[i] = w[i];
@@ -126,7 +127,7 @@ __global__ __launch_bounds__(kSsMaxThreads) void k_ssm_smooth_rows(SsmRowsArgs a
 }
 
 hipError_t launch_ssm_traceback(hipStream_t s, const SsmRec& r, int N, int B) {
-    if (!r.alog || !r.ran || r.n_obs < 1 || r.T < 1 || N < 1 || N > kLgCap || B < 1) return hipErrorInvalidValue;
+    if (!r.alog || !r.ran || r.n_slots < 1 || r.trace_slot < 0 || r.trace_slot >= r.n_slots || r.T < 1 || N < 1 || N > kLgCap || B < 1) return hipErrorInvalidValue;
     const size_t lds = (ss_n4(N) + kTbMaxRows + (size_t)tb_rows(N) * N) * sizeof(int32_t);
     if (lds > 65536) return hipErrorInvalidValue;
     const int threads = std::max(64, std::min(kTbThreads, ((N + 63) / 64) * 64));
@@ -136,7 +137,7 @@ hipError_t launch_ssm_traceback(hipStream_t s, const SsmRec& r, int N, int B) {
 
 hipError_t launch_ssm_smooth_rows(hipStream_t s, const SsmRec& r, const double* w, double* mean, double* var, bool paths,
                                   int N, int S, int B, int threads) {
-    if (!r.hist || !r.alog || r.n_obs < 1 || r.T < 1 || !w || S < 1 || S > WSMC_SSM_MAX_COLS || N < 1 || N > ssm_cap(S) ||
+    if (!r.hist || !r.alog || r.n_slots < 1 || r.trace_slot < 0 || r.trace_slot >= r.n_slots || r.T < 1 || !w || S < 1 || S > WSMC_SSM_MAX_COLS || N < 1 || N > ssm_cap(S) ||
         B < 1 || (int64_t)B * r.T > INT32_MAX || threads < 64 || threads > kSsMaxThreads || (threads & 63))
         return hipErrorInvalidValue;
     // the fused kernel's layout without the ancestors: S + 1 column buffers, the log-weights, the scratch

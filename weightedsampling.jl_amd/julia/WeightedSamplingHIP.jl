@@ -765,6 +765,7 @@ struct WsmcSsmStmt
     dist::WsmcDist
     value::WsmcOperand
     prog::NTuple{32,WsmcXInst}
+    target::WsmcDist   # SSM_SAMPLE_IMPORTANCE: the target (the struct's last member)
 end
 struct WsmcSsmSpec
     n_cols::Int32
@@ -776,6 +777,7 @@ struct WsmcSsmSpec
     step::NTuple{8,WsmcSsmStmt}
 end
 const SSM_SAMPLE, SSM_ASSIGN, SSM_ASSIGN_EXPR, SSM_OBSERVE = Int32(0), Int32(1), Int32(2), Int32(3)
+const SSM_SAMPLE_IMPORTANCE, SSM_WEIGHT = Int32(4), Int32(5)
 const OPERAND_DATA = Int32(-2)   # col of an operand slot / a program's COL: column comp of the data table
 
 const _NO_INST = WsmcXInst(Int32(0), Int32(-1), Int32(0), Int32(0), 0.0)
@@ -784,22 +786,29 @@ const _NO_DIST = WsmcDist(FAM_NORMAL, MEAN_AFFINE, Int32(1), Int32(0), ntuple(_ 
 _prog32(prog) = ntuple(k -> k <= length(prog) ? prog[k] : _NO_INST, 32)
 "`col ~ dist` (operands over the spec's local column indices, `OPERAND_DATA` for the step's data)"
 ssm_sample(col::Integer, dist::WsmcDist) =
-    WsmcSsmStmt(SSM_SAMPLE, Int32(col), Int32(0), Int32(0), dist, const_operand(0.0), _prog32(()))
+    WsmcSsmStmt(SSM_SAMPLE, Int32(col), Int32(0), Int32(0), dist, const_operand(0.0), _prog32(()), _NO_DIST)
+"`col ~ importance_kernel(proposal, target)`: the draw from `proposal`, the weights gain logpdf(target, x) - logpdf(proposal, x)"
+ssm_sample(col::Integer, proposal::WsmcDist, target::WsmcDist) =
+    WsmcSsmStmt(SSM_SAMPLE_IMPORTANCE, Int32(col), Int32(0), Int32(0), proposal, const_operand(0.0), _prog32(()), target)
 "`col .= value` (an operand)"
 ssm_assign(col::Integer, value::WsmcOperand) =
-    WsmcSsmStmt(SSM_ASSIGN, Int32(col), Int32(0), Int32(0), _NO_DIST, value, _prog32(()))
+    WsmcSsmStmt(SSM_ASSIGN, Int32(col), Int32(0), Int32(0), _NO_DIST, value, _prog32(()), _NO_DIST)
 "`col .= program` (a postfix program of at most 32 `WsmcXInst`)"
 ssm_assign(col::Integer, prog::AbstractVector{WsmcXInst}) =
-    WsmcSsmStmt(SSM_ASSIGN_EXPR, Int32(col), Int32(length(prog)), Int32(0), _NO_DIST, const_operand(0.0), _prog32(prog))
+    WsmcSsmStmt(SSM_ASSIGN_EXPR, Int32(col), Int32(length(prog)), Int32(0), _NO_DIST, const_operand(0.0), _prog32(prog), _NO_DIST)
 "`value => dist`"
 ssm_observe(value::WsmcOperand, dist::WsmcDist) =
-    WsmcSsmStmt(SSM_OBSERVE, Int32(-1), Int32(0), Int32(0), dist, value, _prog32(()))
+    WsmcSsmStmt(SSM_OBSERVE, Int32(-1), Int32(0), Int32(0), dist, value, _prog32(()), _NO_DIST)
+"`_ ~ dist`, scored at `value` (the `Weight` statement)"
+ssm_weight(value::WsmcOperand, dist::WsmcDist) =
+    WsmcSsmStmt(SSM_WEIGHT, Int32(-1), Int32(0), Int32(0), dist, value, _prog32(()), _NO_DIST)
 
 """
     ssm_spec(cols, init, step; data_dim=1) -> WsmcSsmSpec
 
 The model description of `wsmc_ssm_run`: 1..4 scalar column names, at most 4 `init` and 8 `step`
-statements built with `ssm_sample`, `ssm_assign` and `ssm_observe`.
+statements built with `ssm_sample` (with a target as well: an `importance_kernel` Sample), `ssm_assign`,
+`ssm_observe` and `ssm_weight`.
 """
 function ssm_spec(cols::AbstractVector{<:AbstractString}, init::AbstractVector{WsmcSsmStmt},
                   step::AbstractVector{WsmcSsmStmt}; data_dim::Integer=1)

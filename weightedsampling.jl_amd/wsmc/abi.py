@@ -95,13 +95,13 @@ class MoveSpec(C.Structure):
 # wsmc_ssm_spec (include/wsmc.h): a scalar state-space model for wsmc_ssm_run
 SSM_MAX_COLS, SSM_MAX_INIT, SSM_MAX_STMTS, SSM_MAX_DATA, SSM_XPROG_MAX, SSM_NAME_MAX = 4, 4, 8, 4, 32, 32
 OPERAND_DATA = -2
-SSM_SAMPLE, SSM_ASSIGN, SSM_ASSIGN_EXPR, SSM_OBSERVE = range(4)
+SSM_SAMPLE, SSM_ASSIGN, SSM_ASSIGN_EXPR, SSM_OBSERVE, SSM_SAMPLE_IMPORTANCE, SSM_WEIGHT = range(6)
 
 
 class SsmStmt(C.Structure):
     """wsmc_ssm_stmt: one statement of a wsmc_ssm_spec"""
     _fields_ = [("kind", C.c_int32), ("col", C.c_int32), ("prog_len", C.c_int32), ("reserved", C.c_int32),
-                ("dist", Dist), ("value", Operand), ("prog", XInst * SSM_XPROG_MAX)]
+                ("dist", Dist), ("value", Operand), ("prog", XInst * SSM_XPROG_MAX), ("target", Dist)]
 
 
 class SsmSpec(C.Structure):

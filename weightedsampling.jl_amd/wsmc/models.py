@@ -235,6 +235,26 @@ def lgssm1d_spec(a=0.9, q=1.0, r=0.5, x0_std=1.0):
                   observe(Data(0), Normal(Col("x"), r))))
 
 
+def lgssm1d_guided(a=0.9, q=1.0, r=0.5, x0_std=1.0, gain=None, prop_std=None):
+    """lgssm1d_spec with a guided proposal (columns x, xp, m): x ~ Normal(0, x0_std); step: xp .= x;
+    m .= (1 - gain) a xp + gain y_t; x ~ importance_kernel(Normal(m, prop_std), Normal(a xp, q));
+    y_t => Normal(x, r). The defaults are the optimal proposal p(x_t | x_t-1, y_t): gain =
+    q^2 / (q^2 + r^2), prop_std = sqrt(q^2 r^2 / (q^2 + r^2)). Data: lgssm1d_data."""
+    from .dsl import Data
+    from .ssm import SSM, assign, observe, sample
+    from .transformers import importance_kernel
+    if gain is None:
+        gain = q * q / (q * q + r * r)
+    if prop_std is None:
+        prop_std = math.sqrt(q * q * r * r / (q * q + r * r))
+    return (SSM(cols=["x", "xp", "m"])
+            .init(sample("x", Normal(0.0, x0_std)))
+            .step(assign("xp", Col("x")),
+                  assign("m", Col("xp") * ((1 - gain) * a) + gain * Data(0)),
+                  sample("x", importance_kernel(Normal(Col("m"), prop_std), Normal(Col("xp") * a, q))),
+                  observe(Data(0), Normal(Col("x"), r))))
+
+
 def sv(mu=-1.0, phi=0.95, sigma=0.25):
     """Stochastic volatility: h ~ Normal(0, sigma / sqrt(1 - phi^2)); step: h ~ Normal(mu (1 - phi) +
     phi h, sigma); s .= exp(h / 2); y_t => Normal(0, s)."""

@@ -12,7 +12,13 @@
     ev = ctx.ssm_run(sv, y)                    # one call (a persistent workgroup where it fits)
     sv.statements(ctx_or_oracle, y)            # the same statements, issued one by one
 
-Every `sample` and `observe` is followed by its auto-inserted Resample (what @model inserts); an
+`sample(col, importance_kernel(proposal, target))` is the reference's `x ~ importance_kernel(...)`:
+the draw comes from the proposal and the weights gain logpdf(target, x) - logpdf(proposal, x), both
+read after x is stored (a transition target needs the old state copied to another column first);
+`weight(value, kernel)` is `_ ~ kernel` scored at value. A proposal with lighter tails than its
+target gives weights of unbounded variance: the evidence estimate then gets worse, not better.
+
+Every `sample`, `observe` and `weight` is followed by its auto-inserted Resample (what @model inserts); an
 `assign` whose right-hand side is affine in at most two columns lowers to WSMC_SSM_ASSIGN, every
 other one to WSMC_SSM_ASSIGN_EXPR (a postfix program). `Data(j)` is column j of the run's data
 table at the current step; only `step` may read it.
@@ -28,8 +34,10 @@ from .abi import Operand
 from .dsl import DATA, Expr, Fx, Kernel, xprogram
 
 
-def sample(col: str, kernel: Kernel):
-    """col ~ kernel"""
+def sample(col: str, kernel):
+    """col ~ kernel, or col ~ importance_kernel(proposal, target) (wsmc.importance_kernel)"""
+    if hasattr(kernel, "proposal") and hasattr(kernel, "target"):
+        return (abi.SSM_SAMPLE_IMPORTANCE, str(col), kernel)
     return (abi.SSM_SAMPLE, str(col), kernel)
 
 
@@ -43,10 +51,20 @@ def observe(value, kernel: Kernel):
     return (abi.SSM_OBSERVE, value, kernel)
 
 
+def weight(value, kernel: Kernel):
+    """_ ~ kernel, scored at value"""
+    return (abi.SSM_WEIGHT, value, kernel)
+
+
 def _general(rhs) -> bool:
     """the right-hand side needs a program: an Fx, or an affine form whose merged operand would
     round differently from the user's own order (Expr.fx)"""
-    return isinstance(rhs, Fx) or (isinstance(rhs, Expr) and rhs.fx is not None)
+    if isinstance(rhs, Fx) or (isinstance(rhs, Expr) and rhs.fx is not None):
+        return True
+    # a data reference the operand form cannot fold exactly (a scaled one, one beside a constant,
+    # two of them): the same affine form as a program, where a data read is a leaf
+    data = [coef for name, _, coef in rhs.terms if name == DATA] if isinstance(rhs, Expr) else []
+    return bool(data) and (len(data) > 1 or data[0] != 1.0 or rhs.c0 != 0.0)
 
 
 def batch_arguments(specs, data, n, seeds, T=None):
@@ -222,7 +240,11 @@ class SSM:
         if kind == abi.SSM_SAMPLE:
             out.col = self._resolve(st[1])
             out.dist = st[2].dist(self._resolve)
-        elif kind == abi.SSM_OBSERVE:
+        elif kind == abi.SSM_SAMPLE_IMPORTANCE:
+            out.col = self._resolve(st[1])
+            out.dist = st[2].proposal.dist(self._resolve)
+            out.target = st[2].target.dist(self._resolve)
+        elif kind in (abi.SSM_OBSERVE, abi.SSM_WEIGHT):
             out.value = Expr.lift(st[1]).operand(self._resolve)
             out.dist = st[2].dist(self._resolve)
         elif _general(st[2]):
@@ -262,7 +284,7 @@ class SSM:
         used = -1
         for q in range(sp.n_init + sp.n_step):
             s = sp.init[q] if q < sp.n_init else sp.step[q - sp.n_init]
-            ops = list(s.dist.mu) + [s.dist.scale, s.value]
+            ops = list(s.dist.mu) + [s.dist.scale, s.value] + list(s.target.mu) + [s.target.scale]
             for o in ops:
                 for k in range(2):
                     if o.col[k] == abi.OPERAND_DATA:
@@ -356,12 +378,26 @@ class SSM:
         def prepare(s):
             """(call, patch): call(waited) issues the statement and its Resample"""
             patch = []
-            out = ids[s.col] if s.kind != abi.SSM_OBSERVE else -1
+            out = ids[s.col] if s.kind not in (abi.SSM_OBSERVE, abi.SSM_WEIGHT) else -1
             if s.kind == abi.SSM_SAMPLE:
                 d = fold_dist(s.dist, patch)
 
                 def call(waited):
                     backend.sample(out, d)
+                    backend.resample(ess_perc_min, scheme, wait=False)
+            elif s.kind == abi.SSM_SAMPLE_IMPORTANCE:
+                d = fold_dist(s.dist, patch)
+                tg = fold_dist(s.target, patch)
+
+                def call(waited):
+                    backend.sample_importance(out, d, tg)
+                    backend.resample(ess_perc_min, scheme, wait=False)
+            elif s.kind == abi.SSM_WEIGHT:
+                d = fold_dist(s.dist, patch)
+                x = [fold_operand(s.value, patch)]
+
+                def call(waited):
+                    backend.weight(d, x)
                     backend.resample(ess_perc_min, scheme, wait=False)
             elif s.kind == abi.SSM_ASSIGN:
                 e = [fold_operand(s.value, patch)]
