@@ -647,6 +647,108 @@ int wsmc_ssm_run_batch_smoothed(wsmc_ctx* ctx, const wsmc_ssm_spec* specs, int32
  * segments, of the trace-back (phase 1) and of the rows kernel (phase 2), microseconds, and the
  * bytes the call allocated for the log and the rows. */
 int wsmc_debug_ssm_smooth(wsmc_ctx* ctx, int64_t* stats_out);
+/* ---- backward simulation: trajectories that do not collapse ------------------------------------
+ * The genealogy above degenerates once T exceeds about n steps: every final particle then shares
+ * one ancestor. Forward filtering, backward simulation keeps the filter's particles and weights at
+ * every trace point (the record) and draws each of M trajectories backwards: at t = T-1 by the
+ * last weights (src/utils.jl's `sample`, wsmc_sample_particles with replace), at t < T-1 with
+ * particle i reweighted by the density of going from i to the successor already drawn, the
+ * `logpdf` fields of src/default_kernels.jl's kernels.
+ *
+ * Which terms enter, and which specs are eligible (host only, no context). Walk `step` once with
+ * every column tainted (it holds the previous trace point's value); z is the successor's row:
+ *   SAMPLE col ~ dist        logpdf(dist, z[col]) is included iff an operand of dist reads a
+ *                            tainted column (operands are read before the store, so its own column
+ *                            counts as old); then col is untainted and holds z[col]
+ *   SAMPLE_IMPORTANCE        col takes z[col] and is untainted; logpdf(target, z[col]) is included
+ *                            iff an operand of target then reads a tainted column; the proposal is
+ *                            not part of the model and never enters
+ *   ASSIGN / ASSIGN_EXPR     col is tainted iff the right-hand side reads a tainted column; it
+ *                            takes the computed value, never z[col]
+ *   OBSERVE / WEIGHT         its logpdf is included iff its dist or value reads a tainted column
+ * included[q] is set to 1 for an included statement q of `step`, else 0. WSMC_EARG, with the
+ * reason in wsmc_last_error(): a spec wsmc_ssm_spec_check refuses; (a) the step's last statement is
+ * not its last OBSERVE, the trace point; (b) a column written by a SAMPLE of either kind is
+ * written by another statement of the step; (c) a state column, one that a statement of the step
+ * reads before the step overwrites it, is tainted at the end of the step: a static parameter, a lag
+ * carried by assignment, any deterministic carry-over (the transition is a Dirac and backward
+ * simulation is not defined).
+ * Caveat: an auxiliary column assigned from the old state (x / 2 + ... of the previous x, a copy
+ * of it) holds in row t+1 of a drawn trajectory the filter particle's own value: f of that
+ * particle's genealogical parent, not f of the drawn x_t. */
+int wsmc_ssm_spec_backward(const wsmc_ssm_spec* spec, int32_t included[WSMC_SSM_MAX_STMTS]);
+/* The results of a backward pass: caller-owned host buffers, each may be NULL (not wanted).
+ * idx[t][m] is the filter particle trajectory m passes through at trace point t; paths[t][k][m] =
+ * particles[t][k][idx[t][m]]; mean[t][k] and var[t][k] are wsmc_weighted_moments of row t of paths
+ * (d = n_cols, expression k = paths[t][k] alone) on M particles with fresh (equal) weights. */
+typedef struct {
+    int32_t* idx;               /* [T][M]          */
+    double*  paths;             /* [T][n_cols][M]  */
+    double*  mean;              /* [T][n_cols]     */
+    double*  var;               /* [T][n_cols]     */
+    double*  particles;         /* [T][n_cols][n]  the record (wsmc_ssm_run_backward) */
+    double*  log_weights;       /* [T][n]          */
+} wsmc_ssm_backward_out;
+/* sizeof(wsmc_ssm_backward_out) as the library was built (layout check) */
+int wsmc_ssm_backward_out_sizeof(int64_t* bytes);
+/* The backward pass over a record the caller supplies: particles [T][n_cols][n] and log_weights
+ * [T][n] at the trace points of a run of `spec` over `data` (T x data_dim). Bit for bit what these
+ * operators give, for trajectory m = 0 .. M-1 and t = T-1 down to 0 on a scratch context of n
+ * particles and seed `seed`: wsmc_weights_upload(log_weights[t]); for t < T-1 wsmc_col_upload of
+ * particles[t] and step t+1's statements in order, data row t+1 folded in, z = particles[t+1][.]
+ * [idx[t+1][m]]: a SAMPLE as wsmc_weight(dist, const z[col]) if included, then wsmc_assign(col,
+ * const z[col]); an importance SAMPLE as wsmc_assign(col, const z[col]), then wsmc_weight(target,
+ * col) if included; an assignment as it is; an OBSERVE or WEIGHT as wsmc_weight(dist, value) if
+ * included; no Resample; then wsmc_set_op_counter(t M + m) and wsmc_sample_particles(1, replace):
+ * idx[t][m]. So the weights sum as ((lw + term_1) + term_2) ... in statement order and the draw is
+ * wsmc_multi_target(wsmc_multi_word(seed, t M + m, 0), Q) on the integer weights, the first index
+ * whose running sum exceeds it. One workgroup a trajectory, t looped on the device.
+ * ctx gives the device and the stream only (as in wsmc_ssm_run_batch): nothing of it is read or
+ * written. n <= 5120 (the record is not held in LDS, so the cap does not depend on n_cols);
+ * 1 <= M <= wsmc_debug_ssm's cap for n_cols columns. out->particles and out->log_weights are not
+ * written. WSMC_EARG: a spec wsmc_ssm_spec_backward refuses, n or M out of range, T < 1, null
+ * record, out or data (with data_dim > 0), more than WSMC_XPROG_MAX program instructions, a
+ * sharded or multi-device ctx. WSMC_ESTATE, the outputs unspecified: wsmc_sample_particles would
+ * return it for some (t, m) (exp_norm of the weights is NaN). WSMC_ENOMEM: the device refuses the
+ * record and the outputs. */
+int wsmc_ssm_backward(wsmc_ctx* ctx, const wsmc_ssm_spec* spec, const double* data, int32_t T,
+                      const double* particles, const double* log_weights, int32_t n, int32_t M,
+                      uint64_t seed, const wsmc_ssm_backward_out* out);
+/* wsmc_ssm_run_traced on the persistent route with the record logged to device memory (every
+ * column and the log-weights at each trace point), and wsmc_ssm_backward's pass over it behind the
+ * last segment on the stream, no host round trip in between. out->particles and out->log_weights
+ * return the record if asked for. Everything the run leaves on ctx (columns, weights, ancestors,
+ * state fields, tape, evidence, RNG positions, the filtering trace if asked) is bit for bit
+ * wsmc_ssm_run_traced's; the backward pass draws from `seed`, not from the context's stream.
+ * The call has the persistent route only: wsmc_ssm_run_smoothed's refusals and
+ * wsmc_ssm_spec_backward's, M < 1 or above the cap, null out: WSMC_EARG with the context as it
+ * was. WSMC_ENOMEM, the context as it was, when the device refuses the 8 T n (n_cols + 1) bytes of
+ * the record plus the outputs. WSMC_ESTATE as above: the run itself is then complete. The genealogy
+ * pass of wsmc_ssm_run_smoothed rewrites its history in place, so there is no `smooth` argument: a
+ * caller who wants both makes two calls. */
+int wsmc_ssm_run_backward(wsmc_ctx* ctx, const wsmc_ssm_spec* spec, const double* data, int32_t T,
+                          double ess_perc_min, int32_t scheme, double* log_evidence_out,
+                          const wsmc_ssm_trace* trace, int32_t M, uint64_t seed,
+                          const wsmc_ssm_backward_out* out);
+/* wsmc_ssm_run_batch_traced with wsmc_ssm_run_backward's pass for every filter: filter b is, bit for
+ * bit, what wsmc_ssm_run_backward gives on a fresh wsmc_create(n, seeds[b]) context with
+ * bw_seeds[b]. Every array of bw_out is [B]-leading (idx [B][T][M], paths [B][T][n_cols][M], mean and
+ * var [B][T][n_cols], particles [B][T][n_cols][n], log_weights [B][T][n]). wsmc_ssm_run_batch's
+ * refusals, wsmc_ssm_spec_backward's for every spec ("spec b: ..."), M < 1 or above the cap, null
+ * bw_seeds or bw_out: WSMC_EARG. The record and the outputs of all B filters are part of the call's
+ * device allocation: WSMC_ENOMEM when the device refuses it. WSMC_ESTATE, the backward outputs
+ * unspecified, when a draw of any filter fails; the filters themselves are then complete. */
+int wsmc_ssm_run_batch_backward(wsmc_ctx* ctx, const wsmc_ssm_spec* specs, int32_t n_specs,
+                                const double* data, int32_t n_tables, int32_t T, int32_t n, int32_t B,
+                                const uint64_t* seeds, double ess_perc_min, int32_t scheme,
+                                wsmc_ssm_batch_out* out, const wsmc_ssm_trace* trace, int32_t M,
+                                const uint64_t* bw_seeds, const wsmc_ssm_backward_out* bw_out);
+/* stats_out[5] = the last backward pass on ctx: device time (HIP events on the stream) of the
+ * run's segments (0 for wsmc_ssm_backward), of the backward kernel and of the rows and moments
+ * kernel, microseconds, and the bytes the call allocated for the record and the outputs; then the
+ * segments launched on the backward-recording kernels, cumulative per context (no other entry
+ * point launches them). */
+int wsmc_debug_ssm_backward(wsmc_ctx* ctx, int64_t* stats_out);
 /* per-kernel timing of the last fused run (HIP events on the ctx stream), ms */
 typedef struct {
     double total_ms;            /* whole run, first kernel to last                       */

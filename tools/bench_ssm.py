@@ -47,7 +47,17 @@ leg's protocol (alternating routes, rounds of half a second, the median of three
 warm-up round with their range): models.lgssm1d_guided() through Context.ssm_run, through
 spec.statements on a Context (asynchronous Resamples) and through the library's statement loop
 (a foreign column present), and models.lgssm1d_spec() through Context.ssm_run for scale (the
-bootstrap filter of the same model on the unguided kernel). Lines go to profiles/ssm_guided.jsonl."""
+bootstrap filter of the same model on the unguided kernel). Lines go to profiles/ssm_guided.jsonl.
+
+    python tools/bench_ssm.py --backward                 lgssm and sv at T = 1e3, M = 64 and 1024
+    python tools/bench_ssm.py --backward --leg sv --T 1000 --M 64
+
+The backward leg (wsmc_ssm_run_backward), forced resampling, the smooth leg's protocol: the
+persistent run untraced, the run with M backward-simulated trajectories (the whole call), the
+smoothed run with paths for context, and on the same box a vectorised numpy FFBS of the same
+sizes over the run's own record (the baseline: float64 numpy, its own random stream, not
+bit-compared). The backward kernel's and the rows kernel's device times are the library's own (HIP
+events, Context.ssm_backward_stats). Lines go to profiles/ssm_backward.jsonl."""
 import argparse
 import json
 import pathlib
@@ -64,6 +74,7 @@ OUT = ROOT / "profiles" / "ssm_fused.jsonl"
 OUT_TRACE = ROOT / "profiles" / "ssm_trace.jsonl"
 OUT_SMOOTH = ROOT / "profiles" / "ssm_smooth.jsonl"
 OUT_GUIDED = ROOT / "profiles" / "ssm_guided.jsonl"
+OUT_BACKWARD = ROOT / "profiles" / "ssm_backward.jsonl"
 
 
 def best_of(run, reps=2):
@@ -345,6 +356,120 @@ def child_guided(T: int) -> dict:
     return out
 
 
+def numpy_ffbs(leg, rec, M, rng):
+    """forward filtering, backward simulation over a record, vectorised over the M trajectories: the
+    transition density of lgssm1d_spec / sv at their default parameters, the categorical draws by a
+    cumulative sum and a search. Returns idx [T, M]"""
+    import numpy as np
+    a, b, sd = (0.9, 0.0, 1.0) if leg == "lgssm" else (0.95, -1.0 * (1.0 - 0.95), 0.25)
+    x, lw = rec.cols[:, 0, :], rec.log_weights
+    T, n = lw.shape
+
+    def draw(logw):   # [M, n] -> [M]
+        w = np.exp(logw - logw.max(axis=1, keepdims=True))
+        c = np.cumsum(w, axis=1)
+        u = rng.random(len(c)) * c[:, -1]
+        return np.minimum((c <= u[:, None]).sum(axis=1), n - 1)
+
+    idx = np.empty((T, M), dtype=np.int64)
+    idx[T - 1] = draw(np.broadcast_to(lw[T - 1], (M, n)))
+    for t in range(T - 2, -1, -1):
+        z = x[t + 1][idx[t + 1]]
+        r = (z[:, None] - (a * x[t][None, :] + b)) / sd
+        idx[t] = draw(lw[t][None, :] - 0.5 * r * r)
+    return idx
+
+
+def child_backward(leg: str, T: int, M: int) -> dict:
+    import statistics
+    import numpy as np
+    import wsmc
+    from wsmc import models
+    spec, data = (models.lgssm1d_spec(), models.lgssm1d_data(T)) if leg == "lgssm" else (models.sv(), models.sv_data(T))
+    spec.check()
+    last = {}
+
+    def untraced(ctx):
+        last["untraced"] = ctx.ssm_run(spec, data, ess_perc_min=1.0)
+
+    def backward(ctx):
+        last["backward"] = ctx.ssm_run(spec, data, ess_perc_min=1.0, backward=M, backward_seed=7), ctx.ssm_backward_stats()
+
+    def smoothed(ctx):
+        last["smoothed"] = ctx.ssm_run(spec, data, ess_perc_min=1.0, smooth=True)
+
+    routes = {"untraced": untraced, "backward": backward, "smoothed": smoothed}
+    times = {k: [] for k in routes}
+    reps = {k: 1 for k in routes}
+    for rnd in range(5):   # round 0 warms up, round 1 sizes the windows, rounds 2..4 are the figures
+        for name, run in routes.items():
+            ctxs = [wsmc.Context(N, seed=42) for _ in range(reps[name])]
+            for c in ctxs:
+                c.sync()
+            t0 = time.perf_counter()
+            for c in ctxs:
+                run(c)
+            dt = (time.perf_counter() - t0) / len(ctxs)
+            for c in ctxs:
+                c.close()
+            if rnd == 1:
+                reps[name] = max(1, min(64, int(0.5 / dt) + 1))
+            if rnd >= 2:
+                times[name].append(dt)
+    (ev_b, bw), st = last["backward"]
+    assert ev_b == last["untraced"] == last["smoothed"][0]
+    g = wsmc.Context(N, seed=42)
+    rec = g.ssm_run(spec, data, ess_perc_min=1.0, backward=M, backward_seed=7, record=True)[1].record
+    g.close()
+    rng = np.random.default_rng(7)
+    t0 = time.perf_counter()
+    numpy_ffbs(leg, rec, M, rng)   # a warm-up, which also sizes the repetitions
+    ft = []
+    for _ in range(3 if time.perf_counter() - t0 < 3.0 else 1):
+        t0 = time.perf_counter()
+        fidx = numpy_ffbs(leg, rec, M, rng)
+        ft.append(time.perf_counter() - t0)
+    col = spec.cols[0]
+    sm = last["smoothed"][1]
+    fpaths = np.take_along_axis(rec.cols[:, 0, :], fidx, axis=1)
+    med = {k: statistics.median(v) for k, v in times.items()}
+    out = {"leg": leg, "N": N, "T": T, "M": M, "columns": len(spec.cols), "runs_per_round": reps, "log_evidence": ev_b,
+           "bytes": st["bytes"]}
+    for k in routes:
+        out[f"{k}_s"] = med[k]
+        out[f"{k}_s_range"] = [min(times[k]), max(times[k])]
+    out.update(segments_device_s=st["segments_s"], backward_device_s=st["backward_s"], rows_device_s=st["rows_s"],
+               backward_ns_per_evaluation=1e9 * st["backward_s"] / (T * M * N),
+               numpy_ffbs_s=statistics.median(ft), numpy_ffbs_s_range=[min(ft), max(ft)],
+               numpy_ffbs_ns_per_evaluation=1e9 * statistics.median(ft) / (T * M * N),
+               numpy_over_backward_call=statistics.median(ft) / (med["backward"] - med["untraced"]),
+               # the estimates' shape, for context (not a comparison of bits): distinct values in the first row, the
+               # variance of the state's first-half rows
+               distinct_first_row={"backward": int(len(np.unique(bw.paths[col][0]))), "genealogy": int(len(np.unique(sm.paths[col][0]))),
+                                   "numpy_ffbs": int(len(np.unique(fpaths[0])))},
+               mean_var_first_half={"backward": float(np.mean(bw.var[col][:T // 2])), "genealogy": float(np.mean(sm.var[col][:T // 2])),
+                                    "numpy_ffbs": float(np.mean(fpaths[:T // 2].var(axis=1)))})
+    return out
+
+
+def driver_backward(Ts, legs, Ms) -> int:
+    OUT_BACKWARD.parent.mkdir(exist_ok=True)
+    for leg in legs:
+        for T in Ts:
+            for M in Ms:
+                cmd = ["timeout", "-k", "10", "240", sys.executable, __file__, "--backward", "--leg", leg, "--T", str(T), "--M", str(M)]
+                r = subprocess.run(cmd, capture_output=True, text=True)
+                if r.returncode != 0:
+                    print(f"{leg} T={T} M={M}: exit {r.returncode}\n{r.stdout}\n{r.stderr}", flush=True)
+                    return 1   # nothing more is started on the device
+                line = r.stdout.strip().splitlines()[-1]
+                json.loads(line)
+                with open(OUT_BACKWARD, "a") as f:
+                    f.write(line + "\n")
+                print(line, flush=True)
+    return 0
+
+
 def driver(Ts, legs, trace=False, smooth=False, guided=False) -> int:
     out = OUT_GUIDED if guided else OUT_SMOOTH if smooth else OUT_TRACE if trace else OUT
     OUT.parent.mkdir(exist_ok=True)
@@ -379,7 +504,14 @@ if __name__ == "__main__":
     ap.add_argument("--trace", action="store_true", help="the trace leg (profiles/ssm_trace.jsonl)")
     ap.add_argument("--smooth", action="store_true", help="the smooth leg (profiles/ssm_smooth.jsonl)")
     ap.add_argument("--guided", action="store_true", help="the guided leg (profiles/ssm_guided.jsonl)")
+    ap.add_argument("--backward", action="store_true", help="the backward leg (profiles/ssm_backward.jsonl)")
+    ap.add_argument("--M", type=int, action="append", help="the backward leg's trajectories")
     a = ap.parse_args()
+    if a.backward and a.leg:
+        print(json.dumps(child_backward(a.leg, (a.T or [1000])[0], (a.M or [64])[0])), flush=True)
+        sys.exit(0)
+    if a.backward:
+        sys.exit(driver_backward(a.T or [1000], a.legs.split(",") if a.legs != ",".join(LEGS) else ["lgssm", "sv"], a.M or [64, 1024]))
     if a.guided and a.T and len(a.T) == 1:
         print(json.dumps(child_guided(a.T[0])), flush=True)
         sys.exit(0)

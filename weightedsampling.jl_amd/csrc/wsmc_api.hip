@@ -5787,28 +5787,278 @@ struct SsmSmoothClock {
         return hipSuccess;
     }
     hipError_t mark(int k, hipStream_t s) { return on ? hipEventRecord(ev[k], s) : hipSuccess; }
-    void read(wsmc_ctx* c, size_t bytes) {   // after the stream's end
+    void elapsed(int64_t* us3) {   // after the stream's end
         for (int k = 0; k < 3; ++k) {
             float ms = 0.0f;
-            c->ssm_smooth_us[k] = on && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess ? (int64_t)(ms * 1000.0f) : 0;
+            us3[k] = on && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess ? (int64_t)(ms * 1000.0f) : 0;
         }
+    }
+    void read(wsmc_ctx* c, size_t bytes) {
+        elapsed(c->ssm_smooth_us);
         c->ssm_smooth_bytes = (int64_t)bytes;
     }
 };
-static int ssm_smooth_alloc(SsmSlab* slab, size_t bytes, const char* who) {
+static int ssm_smooth_alloc(SsmSlab* slab, size_t bytes, const char* who, const char* what = "the history and the ancestor log") {
     const hipError_t e = hipMalloc(&slab->p, bytes);
     if (e == hipSuccess) return WSMC_OK;
     slab->p = nullptr;
     (void)hipGetLastError();
     if (e == hipErrorOutOfMemory)
-        return fail(WSMC_ENOMEM, std::string(who) + ": the device refused " + std::to_string(bytes) + " bytes for the history and the ancestor log");
+        return fail(WSMC_ENOMEM, std::string(who) + ": the device refused " + std::to_string(bytes) + " bytes for " + what);
     return fail(WSMC_EHIP, std::string(who) + ": hipMalloc: " + hipGetErrorString(e));
+}
+
+// ---- backward simulation over a run's record (csrc/wsmc_ssm_backward.hip) ------------------------
+// the spec columns an operand / a dist / a program reads, as a bit mask (a data slot is no column)
+static unsigned ssm_operand_reads(const wsmc_operand& o) {
+    return (o.col[0] >= 0 ? 1u << o.col[0] : 0u) | (o.col[1] >= 0 ? 1u << o.col[1] : 0u);
+}
+static unsigned ssm_dist_reads(const wsmc_dist& d) { return ssm_operand_reads(d.mu[0]) | ssm_operand_reads(d.scale); }
+static unsigned ssm_prog_reads(const wsmc_ssm_stmt& s) {
+    unsigned r = 0;
+    for (int q = 0; q < s.prog_len; ++q)
+        if (s.prog[q].op == WSMC_X_COL && s.prog[q].col >= 0) r |= 1u << s.prog[q].col;
+    return r;
+}
+// wsmc_ssm_spec_backward's rule on a checked spec (include/wsmc.h): the included statements of
+// `step`, or the first reason backward simulation is not defined for the spec
+static std::string ssm_backward_why(const wsmc_ssm_spec* sp, int32_t* included) {
+    const int S = sp->n_cols, n = sp->n_step;
+    for (int q = 0; q < WSMC_SSM_MAX_STMTS; ++q) included[q] = 0;
+    if (sp->step[n - 1].kind != WSMC_SSM_OBSERVE) return "the step's last statement is not its last OBSERVE (the trace point)";
+    int drawn[WSMC_SSM_MAX_COLS] = {0, 0, 0, 0}, writes[WSMC_SSM_MAX_COLS] = {0, 0, 0, 0};
+    for (int q = 0; q < n; ++q) {
+        const wsmc_ssm_stmt& s = sp->step[q];
+        if (ssm_is_weigh(s.kind)) continue;
+        writes[s.col] += 1;
+        drawn[s.col] += ssm_is_sample(s.kind);
+    }
+    for (int k = 0; k < S; ++k)
+        if (drawn[k] && writes[k] > 1)
+            return std::string("column ") + sp->col_names[k] + " is written by a SAMPLE and by another statement of the step";
+    unsigned tainted = (1u << S) - 1u, written = 0, state = 0;
+    for (int q = 0; q < n; ++q) {
+        const wsmc_ssm_stmt& s = sp->step[q];
+        if (s.kind == WSMC_SSM_SAMPLE) {   // its operands are read before the store: its own column counts as old
+            const unsigned r = ssm_dist_reads(s.dist);
+            state |= r & ~written;
+            included[q] = (r & tainted) != 0;
+            tainted &= ~(1u << s.col);
+            written |= 1u << s.col;
+        } else if (s.kind == WSMC_SSM_SAMPLE_IMPORTANCE) {   // the draw reads the proposal before the store, the target after it
+            state |= ssm_dist_reads(s.dist) & ~written;
+            tainted &= ~(1u << s.col);
+            written |= 1u << s.col;
+            const unsigned r = ssm_dist_reads(s.target);
+            state |= r & ~written;
+            included[q] = (r & tainted) != 0;
+        } else if (s.kind == WSMC_SSM_ASSIGN || s.kind == WSMC_SSM_ASSIGN_EXPR) {
+            const unsigned r = s.kind == WSMC_SSM_ASSIGN ? ssm_operand_reads(s.value) : ssm_prog_reads(s);
+            state |= r & ~written;
+            tainted = (r & tainted) ? tainted | (1u << s.col) : tainted & ~(1u << s.col);
+            written |= 1u << s.col;
+        } else {
+            const unsigned r = ssm_dist_reads(s.dist) | ssm_operand_reads(s.value);
+            state |= r & ~written;
+            included[q] = (r & tainted) != 0;
+        }
+    }
+    for (int k = 0; k < S; ++k)
+        if (state & tainted & (1u << k))
+            return std::string("state column ") + sp->col_names[k] +
+                   " still holds the previous step's value at the end of the step (a static parameter or a deterministic "
+                   "carry-over: the transition is a Dirac)";
+    return std::string();
+}
+
+int wsmc_ssm_spec_backward(const wsmc_ssm_spec* spec, int32_t* included) {
+    if (!included) return fail(WSMC_EARG, "null argument");
+    if (int rc = wsmc_ssm_spec_check(spec)) return rc;
+    const std::string why = ssm_backward_why(spec, included);
+    if (!why.empty()) return fail(WSMC_EARG, "ssm backward: " + why);
+    return WSMC_OK;
+}
+
+int wsmc_ssm_backward_out_sizeof(int64_t* bytes) {
+    if (!bytes) return fail(WSMC_EARG, "null argument");
+    *bytes = (int64_t)sizeof(wsmc_ssm_backward_out);
+    return WSMC_OK;
+}
+
+// what a call asks of the backward pass (checked: wsmc_ssm_backward's arguments)
+struct SsmBwReq {
+    int32_t M;
+    uint64_t seed;
+    wsmc_ssm_backward_out out;
+    int32_t included[WSMC_SSM_MAX_STMTS];
+};
+// the spec and the pass's own arguments, before any device call: `included`, or the refusal
+static int ssm_bw_check(const wsmc_ctx* c, const wsmc_ssm_spec* sp, int32_t M, const wsmc_ssm_backward_out* out, const char* who,
+                        SsmBwReq* req) {
+    if (int rc = wsmc_ssm_spec_check(sp)) return rc;
+    const std::string why = ssm_backward_why(sp, req->included);
+    if (!why.empty()) return fail(WSMC_EARG, "ssm backward: " + why);
+    if (!out) return fail(WSMC_EARG, std::string(who) + ": null out");
+    if (c->multi || is_sharded(c)) return fail(WSMC_EARG, std::string(who) + ": a sharded or multi-device context (one unsharded device runs it)");
+    if (M < 1 || M > ssm_cap(sp->n_cols))
+        return fail(WSMC_EARG, std::string(who) + ": M = " + std::to_string(M) + " trajectories (1 .. " + std::to_string(ssm_cap(sp->n_cols)) +
+                                   " for " + std::to_string(sp->n_cols) + " columns)");
+    req->M = M;
+    req->out = *out;
+    return WSMC_OK;
+}
+// The pass's device buffers for B filters of n particles (dd: the table's columns where the pass holds its own copy), carved from `base` (null: the sizes
+// alone): the record, then the indices and the flag (zeroed before the pass), the filter's step,
+// the data table and the outputs. Returns the bytes
+struct SsmBwBufs {
+    double *hist, *lwlog;
+    int32_t *idx, *flag;
+    SsmBwFilter* filt;
+    double *data, *paths, *mean, *var;
+    size_t zero_off, zero_bytes;
+};
+static size_t ssm_bw_carve(char* base, int64_t B, int64_t T, int64_t n, int64_t M, int S, int dd, SsmBwBufs* out) {
+    const size_t nhist = ssm_up(sizeof(double) * (size_t)B * T * S * n), nlw = ssm_up(sizeof(double) * (size_t)B * T * n),
+                 nidx = ssm_up(sizeof(int32_t) * (size_t)B * T * M), nflag = 256, nfilt = ssm_up(sizeof(SsmBwFilter) * (size_t)B),
+                 ndata = ssm_up(sizeof(double) * (size_t)T * dd), npaths = ssm_up(sizeof(double) * (size_t)B * T * S * M),
+                 nrow = ssm_up(sizeof(double) * (size_t)B * T * S);
+    if (out) {
+        char* q = base;
+        out->hist = reinterpret_cast<double*>(q); q += nhist;
+        out->lwlog = reinterpret_cast<double*>(q); q += nlw;
+        out->zero_off = (size_t)(q - base);
+        out->zero_bytes = nidx + nflag;
+        out->idx = reinterpret_cast<int32_t*>(q); q += nidx;
+        out->flag = reinterpret_cast<int32_t*>(q); q += nflag;
+        out->filt = reinterpret_cast<SsmBwFilter*>(q); q += nfilt;
+        out->data = reinterpret_cast<double*>(q); q += ndata;
+        out->paths = reinterpret_cast<double*>(q); q += npaths;
+        out->mean = reinterpret_cast<double*>(q); q += nrow;
+        out->var = reinterpret_cast<double*>(q);
+    }
+    return nhist + nlw + nidx + nflag + nfilt + ndata + npaths + 2 * nrow;
+}
+// the step as k_ssm_backward reads it (its programs' offsets count from the step's first instruction)
+static void ssm_bw_filter(const wsmc_ssm_spec* sp, const SsmBwReq& req, const double* d_data, SsmBwFilter* f) {
+    std::memset(f, 0, sizeof(*f));
+    int nins = 0;
+    for (int q = 0; q < sp->n_step; ++q) {
+        const wsmc_ssm_stmt& s = sp->step[q];
+        f->step[q] = ssm_dev_stmt(s, f->ins, &nins);
+        f->included[q] = req.included[q];
+        if (s.kind != WSMC_SSM_SAMPLE_IMPORTANCE) continue;
+        SsmTarget& r = f->targ[q];
+        r.family = s.target.family;
+        r.mu = s.target.mu[0];
+        r.scale = s.target.scale;
+        r.param[0] = s.target.param[0];
+        r.param[1] = s.target.param[1];
+    }
+    f->seed = req.seed;
+    f->data = d_data;
+}
+// the filters' steps and the pass's own data table (if any) to the device and the indices and the flag zeroed, ahead of the pass
+static hipError_t ssm_bw_stage(hipStream_t st, char* base, const SsmBwBufs& bb, const SsmBwFilter* f, int64_t B, const double* data, size_t ndata) {
+    hipError_t e = hipMemsetAsync(base + bb.zero_off, 0, bb.zero_bytes, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(bb.filt, f, sizeof(SsmBwFilter) * (size_t)B, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && ndata > 0) e = hipMemcpyAsync(bb.data, data, sizeof(double) * ndata, hipMemcpyHostToDevice, st);
+    return e;
+}
+// the pass on the stream behind the record's last write: the backward kernel, the rows kernel
+// (the clock's marks 2 and 3 behind them) and the outputs' downloads; *hflag is valid after the stream's end
+static hipError_t ssm_bw_pass(hipStream_t st, const SsmBwBufs& bb, const SsmShape& sh, int32_t B, int32_t T, int32_t n, const SsmBwReq& req,
+                              SsmSmoothClock& clock, int32_t* hflag) {
+    const int M = req.M, S = sh.S;
+    const wsmc_ssm_backward_out& out = req.out;
+    SsmBwArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.hist = bb.hist;
+    a.lwlog = bb.lwlog;
+    a.idx = bb.idx;
+    a.flag = bb.flag;
+    a.filt = bb.filt;
+    const int threads = ssm_backward_threads(n);
+    a.N = n;
+    a.P = (n + threads - 1) / threads;
+    a.S = S;
+    a.data_dim = sh.data_dim;
+    a.T = T;
+    a.M = M;
+    a.n_step = sh.n_step;
+    a.B = B;
+    hipError_t e = launch_ssm_backward(st, a, sh.feat, threads);
+    if (e == hipSuccess) e = clock.mark(2, st);
+    if (e == hipSuccess)
+        e = launch_ssm_backward_rows(st, bb.hist, bb.idx, out.paths ? bb.paths : nullptr, out.mean ? bb.mean : nullptr,
+                                     out.var ? bb.var : nullptr, n, M, S, T, B);
+    if (e == hipSuccess) e = clock.mark(3, st);
+    auto down = [&](void* host, const void* dev, size_t bytes) {
+        if (e == hipSuccess && host) e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st);
+    };
+    down(out.idx, bb.idx, sizeof(int32_t) * (size_t)B * T * M);
+    down(out.paths, bb.paths, sizeof(double) * (size_t)B * T * S * M);
+    down(out.mean, bb.mean, sizeof(double) * (size_t)B * T * S);
+    down(out.var, bb.var, sizeof(double) * (size_t)B * T * S);
+    down(hflag, bb.flag, sizeof(int32_t));
+    return e;
+}
+
+int wsmc_ssm_backward(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int32_t T, const double* particles,
+                      const double* log_weights, int32_t n, int32_t M, uint64_t seed, const wsmc_ssm_backward_out* out) {
+    if (!c) return fail(WSMC_EARG, "null context");
+    SsmBwReq req;
+    if (int rc = ssm_bw_check(c, sp, M, out, "ssm backward", &req)) return rc;
+    req.seed = seed;
+    if (T < 1 || !particles || !log_weights || (sp->data_dim > 0 && !data)) return fail(WSMC_EARG, "ssm backward: bad arguments");
+    if (n < 1 || n > kLgCap)
+        return fail(WSMC_EARG, "ssm backward: n = " + std::to_string(n) + " particles (1 .. " + std::to_string(kLgCap) + ")");
+    const SsmShape sh = ssm_shape(sp);
+    if (sh.nprog > kSsmProgMax)
+        return fail(WSMC_EARG, "ssm backward: " + std::to_string(sh.nprog) + " program instructions (more than " + std::to_string(kSsmProgMax) + ")");
+    const int S = sh.S, dd = sh.data_dim;
+    WSMC_HIP(hipSetDevice(c->device));
+    SsmSlab slab;
+    SsmSmoothClock clock;
+    const size_t bytes = ssm_bw_carve(nullptr, 1, T, n, M, S, dd, nullptr);
+    if (int rc = ssm_smooth_alloc(&slab, bytes + 256, "ssm backward", "the record and the outputs")) return rc;
+    WSMC_HIP(clock.start());
+    SsmBwBufs bb;
+    ssm_bw_carve(slab.p, 1, T, n, M, S, dd, &bb);
+    SsmBwFilter filt;
+    ssm_bw_filter(sp, req, dd > 0 ? bb.data : nullptr, &filt);
+    hipStream_t st = c->stream;
+    // (from here an error leaves through the stream's end, so nothing is freed under a kernel)
+    int32_t hflag = 0;
+    hipError_t e = ssm_bw_stage(st, slab.p, bb, &filt, 1, data, (size_t)T * dd);
+    if (e == hipSuccess) e = hipMemcpyAsync(bb.hist, particles, sizeof(double) * (size_t)T * S * n, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(bb.lwlog, log_weights, sizeof(double) * (size_t)T * n, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = clock.mark(0, st);
+    if (e == hipSuccess) e = clock.mark(1, st);   // (no segments here)
+    if (e == hipSuccess) e = ssm_bw_pass(st, bb, sh, 1, T, n, req, clock, &hflag);
+    const hipError_t es = hipStreamSynchronize(st);   // also after an error: the slab is freed on return
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(WSMC_EHIP, std::string("ssm backward: ") + hipGetErrorString(e));
+    clock.elapsed(c->ssm_bw_us);
+    c->ssm_bw_us[0] = 0;   // (no segments: the two marks' distance is the events' own)
+    c->ssm_bw_bytes = (int64_t)bytes;
+    if (hflag) return fail(WSMC_ESTATE, "ssm backward: exp_norm of the weights is NaN at some step of some trajectory");
+    return WSMC_OK;
+}
+
+int wsmc_debug_ssm_backward(wsmc_ctx* c, int64_t* stats_out) {
+    if (!c) return fail(WSMC_EARG, "null context");
+    if (c->multi) return fail(WSMC_EARG, "ssm backward: a multi-device context");
+    if (!stats_out) return fail(WSMC_EARG, "null stats_out");
+    for (int k = 0; k < 3; ++k) stats_out[k] = c->ssm_bw_us[k];
+    stats_out[3] = c->ssm_bw_bytes;
+    stats_out[4] = c->ssm_bw_launches;
+    return WSMC_OK;
 }
 
 // wsmc_ssm_run, wsmc_ssm_run_traced and wsmc_ssm_run_smoothed: tr's and sm's members are null where
 // nothing is wanted
 static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int32_t T, double ess_min, int32_t scheme,
-                   double* log_evidence_out, const wsmc_ssm_trace& tr, const wsmc_ssm_smooth& sm) {
+                   double* log_evidence_out, const wsmc_ssm_trace& tr, const wsmc_ssm_smooth& sm, const SsmBwReq* bw = nullptr) {
     double* const ess_trace_out = tr.ess;
     if (!c) return fail(WSMC_EARG, "null context");
     if (int rc = wsmc_ssm_spec_check(sp)) return rc;
@@ -5833,6 +6083,8 @@ static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int
     // the statements would leave): refused here, before anything of the context changes
     const bool smooth = sm.paths || sm.mean || sm.var;
     if (smooth && !persistent) return fail(WSMC_EARG, "ssm smoothed run: " + why);
+    // a run that ends in backward simulation (wsmc_ssm_run_backward; never smoothed as well): the same
+    if (bw && !persistent) return fail(WSMC_EARG, "ssm backward run: " + why);
     SsmSlab sm_slab;
     SsmSmoothClock sm_clock;
     size_t sm_bytes = 0;
@@ -5844,6 +6096,15 @@ static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int
         if (int rc = ssm_smooth_alloc(&sm_slab, bytes + 256, "ssm smoothed run")) return rc;
         WSMC_HIP(sm_clock.start());
         ssm_smooth_carve(sm_slab.p, sm, 1, T, c->N, sh, &sb);
+    }
+    SsmBwBufs bb;
+    std::memset(&bb, 0, sizeof(bb));
+    if (bw) {   // the record, the pass's buffers and its outputs in the slab
+        WSMC_HIP(hipSetDevice(c->device));
+        sm_bytes = ssm_bw_carve(nullptr, 1, T, c->N, bw->M, S, sp->data_dim, nullptr);
+        if (int rc = ssm_smooth_alloc(&sm_slab, sm_bytes + 256, "ssm backward run", "the record and the outputs")) return rc;
+        WSMC_HIP(sm_clock.start());
+        ssm_bw_carve(sm_slab.p, 1, T, c->N, bw->M, S, sp->data_dim, &bb);
     }
     for (int k = 0; k < S; ++k)   // the missing ones, in order
         if (int rc = wsmc_col_create(c, sp->col_names[k], 1, &ids[k])) return rc;
@@ -5870,6 +6131,11 @@ static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int
         WSMC_HIP(hipMemcpyAsync(c->lg_data, data, sizeof(double) * (size_t)ndata, hipMemcpyHostToDevice, c->stream));
     WSMC_HIP(hipMemsetAsync(c->lg_rec, 0, sizeof(LgRecord), c->stream));
     if (smooth) WSMC_HIP(hipMemsetAsync(sm_slab.p + sb.flags_off, 0, sb.flags_bytes, c->stream));
+    SsmBwFilter bw_filt;   // (alive until the stream's end, as `targets` below)
+    if (bw) {
+        ssm_bw_filter(sp, *bw, dd > 0 ? bb.data : nullptr, &bw_filt);
+        WSMC_HIP(ssm_bw_stage(c->stream, sm_slab.p, bb, &bw_filt, 1, data, (size_t)ndata));
+    }
     // (a smoothed run's launches: the same arguments and the log; a guided spec's: and its targets)
     SsmGuidedArgs kga;
     std::memset(&kga, 0, sizeof(kga));
@@ -5903,7 +6169,20 @@ static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int
     WSMC_HIP(sm_clock.mark(0, c->stream));
     for (int32_t t0 = 0; t0 < T; t0 += K, ++nseg) {
         set_segment(ka, t0, K, T);
-        if (sh.guided)
+        if (bw) {   // the recording kernels of a backward run: the same arguments, the record's log
+            SsmGuidedBwArgs kgb;
+            std::memset(&kgb, 0, sizeof(kgb));
+            kgb.ra.a = ka;
+            kgb.ra.r.hist = bb.hist;
+            kgb.ra.r.lwlog = bb.lwlog;
+            kgb.ra.r.T = T;
+            kgb.targ = kga.targ;
+            if (sh.guided)
+                WSMC_HIP(launch_ssm_guided_segment_bwrec(c->stream, kgb, feat, threads));
+            else
+                WSMC_HIP(launch_ssm_segment_bwrec(c->stream, kgb.ra, feat, threads));
+            c->ssm_bw_launches += 1;
+        } else if (sh.guided)
             WSMC_HIP(launch_ssm_guided_segment(c->stream, kga, feat, threads, smooth));
         else if (smooth)
             WSMC_HIP(launch_ssm_segment_rec(c->stream, kra, feat, threads));
@@ -5921,6 +6200,17 @@ static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int
                                     c->stream));
         if (sm.mean) WSMC_HIP(hipMemcpyAsync(sm.mean, sb.mean, sizeof(double) * (size_t)T * S, hipMemcpyDeviceToHost, c->stream));
         if (sm.var) WSMC_HIP(hipMemcpyAsync(sm.var, sb.var, sizeof(double) * (size_t)T * S, hipMemcpyDeviceToHost, c->stream));
+    }
+    int32_t bw_flag = 0;
+    if (bw) {   // the backward pass over the record: on the stream, behind the last segment
+        WSMC_HIP(sm_clock.mark(1, c->stream));
+        WSMC_HIP(ssm_bw_pass(c->stream, bb, sh, 1, T, (int32_t)c->N, *bw, sm_clock, &bw_flag));
+        if (bw->out.particles)
+            WSMC_HIP(hipMemcpyAsync(bw->out.particles, bb.hist, sizeof(double) * (size_t)T * S * (size_t)c->N, hipMemcpyDeviceToHost,
+                                    c->stream));
+        if (bw->out.log_weights)
+            WSMC_HIP(hipMemcpyAsync(bw->out.log_weights, bb.lwlog, sizeof(double) * (size_t)T * (size_t)c->N, hipMemcpyDeviceToHost,
+                                    c->stream));
     }
     LgRecord hrec;
     WSMC_HIP(hipMemcpyAsync(&hrec, c->lg_rec, sizeof(LgRecord), hipMemcpyDeviceToHost, c->stream));
@@ -5959,6 +6249,10 @@ static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int
     const auto t_booked = clk::now();
     WSMC_HIP(ctx_sync(c, c->stream));
     if (smooth) sm_clock.read(c, sm_bytes);
+    if (bw) {
+        sm_clock.elapsed(c->ssm_bw_us);
+        c->ssm_bw_bytes = (int64_t)sm_bytes;
+    }
     persistent_leave(c, hrec);
     c->ssm_runs += 1;
     c->ssm_segments += nseg;
@@ -5966,6 +6260,7 @@ static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int
     if (log_evidence_out)
         if (int rc = wsmc_log_evidence(c, log_evidence_out)) return rc;
     c->ssm_wall_us = us(t_in, clk::now());
+    if (bw_flag) return fail(WSMC_ESTATE, "ssm backward run: exp_norm of the weights is NaN at some step of some trajectory (the run itself is complete)");
     return WSMC_OK;
 }
 
@@ -5983,6 +6278,16 @@ int wsmc_ssm_run_traced(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data
 int wsmc_ssm_run_smoothed(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int32_t T, double ess_min, int32_t scheme,
                           double* log_evidence_out, const wsmc_ssm_trace* trace, const wsmc_ssm_smooth* smooth) {
     return ssm_run(c, sp, data, T, ess_min, scheme, log_evidence_out, trace ? *trace : kNoTrace, smooth ? *smooth : kNoSmooth);
+}
+
+int wsmc_ssm_run_backward(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int32_t T, double ess_min, int32_t scheme,
+                          double* log_evidence_out, const wsmc_ssm_trace* trace, int32_t M, uint64_t seed,
+                          const wsmc_ssm_backward_out* out) {
+    if (!c) return fail(WSMC_EARG, "null context");
+    SsmBwReq req;
+    if (int rc = ssm_bw_check(c, sp, M, out, "ssm backward run", &req)) return rc;
+    req.seed = seed;
+    return ssm_run(c, sp, data, T, ess_min, scheme, log_evidence_out, trace ? *trace : kNoTrace, kNoSmooth, &req);
 }
 
 int wsmc_debug_ssm(wsmc_ctx* c, int32_t segment_steps, int64_t* stats_out) {
@@ -6084,7 +6389,8 @@ int wsmc_ssm_batch_out_sizeof(int64_t* bytes) {
 // members are null where nothing is wanted
 static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_specs, const double* data, int32_t n_tables,
                          int32_t T, int32_t n, int32_t B, const uint64_t* seeds, double ess_min, int32_t scheme,
-                         wsmc_ssm_batch_out* out, const wsmc_ssm_trace& tr, const wsmc_ssm_smooth& sm) {
+                         wsmc_ssm_batch_out* out, const wsmc_ssm_trace& tr, const wsmc_ssm_smooth& sm, int32_t bw_M = 0,
+                         const uint64_t* bw_seeds = nullptr, const wsmc_ssm_backward_out* bw_out = nullptr) {
     // every refusal before any device call; the context's state is never read past its layout
     if (!c) return fail(WSMC_EARG, "null context");
     if (B < 1) return fail(WSMC_EARG, "ssm batch: B < 1");
@@ -6139,9 +6445,35 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
     const size_t nstate = nx + nw + nanc + nrec;
     const bool smooth = sm.paths || sm.mean || sm.var;
     const size_t nsmooth = smooth ? ssm_smooth_carve(nullptr, sm, B, T, n, sh, nullptr) : 0;
+    // a batch that ends in backward simulation (wsmc_ssm_run_batch_backward; never smoothed as well): every
+    // spec's included terms (the rule reads kinds and columns alone, but each filter's image is its own)
+    const bool bw = bw_out != nullptr;
+    std::vector<SsmBwFilter> bw_filt(bw ? (size_t)B : 0);
+    SsmBwReq bw_req;
+    if (bw) {
+        if (!bw_seeds) return fail(WSMC_EARG, "ssm batch backward: null bw_seeds");
+        if (bw_M < 1 || bw_M > ssm_cap(S))
+            return fail(WSMC_EARG, "ssm batch backward: M = " + std::to_string(bw_M) + " trajectories (1 .. " + std::to_string(ssm_cap(S)) +
+                                       " for " + std::to_string(S) + " columns)");
+        for (int32_t b = 0; b < B; ++b) {
+            const wsmc_ssm_spec* spb = specs + (n_specs == 1 ? 0 : b);
+            const std::string w = ssm_backward_why(spb, bw_req.included);
+            if (!w.empty()) return fail(WSMC_EARG, "ssm backward: spec " + std::to_string(b) + ": " + w);
+            bw_req.seed = bw_seeds[b];
+            ssm_bw_filter(spb, bw_req, nullptr, &bw_filt[(size_t)b]);   // (.data: set below, the batch's own table)
+        }
+        bw_req.M = bw_M;
+        bw_req.out = *bw_out;
+    }
+    const size_t nbw = bw ? ssm_bw_carve(nullptr, B, T, n, bw_M, S, 0, nullptr) : 0;
     SsmSlab slab;
     SsmSmoothClock sm_clock;
-    if (smooth) {
+    if (bw) {
+        if (int rc = ssm_smooth_alloc(&slab, nstate + nfilt + ndata + ntarg + ntrace + nmean + nvar + nle + nbw + 256, "ssm batch backward",
+                                      "the record and the outputs"))
+            return rc;
+        WSMC_HIP(sm_clock.start());
+    } else if (smooth) {
         if (int rc = ssm_smooth_alloc(&slab, nstate + nfilt + ndata + ntarg + ntrace + nmean + nvar + nle + nsmooth + 256, "ssm smoothed batch"))
             return rc;
         WSMC_HIP(sm_clock.start());
@@ -6168,6 +6500,13 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
     }
     for (int32_t b = 0; b < B; ++b)
         filt[(size_t)b].data = dd > 0 ? d_data + (size_t)(n_tables == 1 ? 0 : b) * T * dd : nullptr;
+    SsmBwBufs bb;
+    std::memset(&bb, 0, sizeof(bb));
+    if (bw) {
+        ssm_bw_carve(q, B, T, n, bw_M, S, 0, &bb);
+        bb.zero_off += (size_t)(q - slab.p);
+        for (int32_t b = 0; b < B; ++b) bw_filt[(size_t)b].data = filt[(size_t)b].data;
+    }
     hipStream_t st = c->stream;
     // (from here an error leaves through the stream's end, so nothing is freed under a kernel)
     auto run = [&]() -> hipError_t {
@@ -6178,6 +6517,7 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
             e = hipMemcpyAsync(d_data, data, sizeof(double) * (size_t)n_tables * T * dd, hipMemcpyHostToDevice, st);
         if (e == hipSuccess && d_targ)
             e = hipMemcpyAsync(d_targ, targ.data(), sizeof(SsmTarget) * targ.size(), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && bw) e = ssm_bw_stage(st, slab.p, bb, bw_filt.data(), B, nullptr, 0);
         return e;
     };
     hipError_t e = run();
@@ -6203,7 +6543,7 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
     // steps a launch: the single run's, divided by the rounds of resident workgroups the batch
     // takes, so a launch stays near the single run's 25 ms whatever B is
     int per_cu = 0, cus = 0;
-    if (e == hipSuccess) e = ssm_batch_occupancy(c->device, feat, sh.guided ? (smooth ? 4 : 3) : smooth ? 2 : (d_mean || d_var || d_le) ? 1 : 0, threads, ssm_lds_bytes(n, S), &per_cu, &cus);
+    if (e == hipSuccess) e = ssm_batch_occupancy(c->device, feat, bw ? (sh.guided ? 6 : 5) : sh.guided ? (smooth ? 4 : 3) : smooth ? 2 : (d_mean || d_var || d_le) ? 1 : 0, threads, ssm_lds_bytes(n, S), &per_cu, &cus);
     if (e == hipSuccess && (per_cu < 1 || cus < 1)) e = hipErrorInvalidValue;
     int64_t nseg = 0;
     if (e == hipSuccess) {
@@ -6215,12 +6555,32 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
         for (int32_t t0 = 0; t0 < T && e == hipSuccess; t0 += K, ++nseg) {
             set_segment(ka, t0, K, T);
             ka.last = t0 + ka.nsteps == T;
+            if (bw) {   // the recording kernels of a backward batch: the same arguments, the record's log
+                SsmBatchGuidedBwArgs kgb;
+                std::memset(&kgb, 0, sizeof(kgb));
+                kgb.ra.a = ka;
+                kgb.ra.r.hist = bb.hist;
+                kgb.ra.r.lwlog = bb.lwlog;
+                kgb.ra.r.T = T;
+                kgb.targ = d_targ;
+                e = sh.guided ? launch_ssm_batch_guided_segment_bwrec(st, kgb, feat, threads) : launch_ssm_batch_segment_bwrec(st, kgb.ra, feat, threads);
+                c->ssm_bw_launches += 1;
+                continue;
+            }
             e = sh.guided ? launch_ssm_batch_guided_segment(st, kga, feat, threads, smooth)
                 : smooth  ? launch_ssm_batch_segment_rec(st, kra, feat, threads)
                           : launch_ssm_batch_segment(st, ka, feat, threads);
         }
     }
     if (e == hipSuccess) e = sm_clock.mark(1, st);
+    int32_t bw_flag = 0;
+    if (e == hipSuccess && bw) {   // the backward pass over every filter's record: behind the last segment
+        e = ssm_bw_pass(st, bb, sh, B, T, n, bw_req, sm_clock, &bw_flag);
+        if (e == hipSuccess && bw_out->particles)
+            e = hipMemcpyAsync(bw_out->particles, bb.hist, sizeof(double) * (size_t)B * T * S * n, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && bw_out->log_weights)
+            e = hipMemcpyAsync(bw_out->log_weights, bb.lwlog, sizeof(double) * (size_t)B * T * n, hipMemcpyDeviceToHost, st);
+    }
     if (e == hipSuccess && smooth) e = launch_ssm_traceback(st, sb.rec, n, B);
     if (e == hipSuccess) e = sm_clock.mark(2, st);
     if (e == hipSuccess && smooth) e = launch_ssm_smooth_rows(st, sb.rec, d_w, sb.mean, sb.var, sm.paths != nullptr, n, S, B, threads);
@@ -6262,10 +6622,15 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
         if (out->last_resampled) out->last_resampled[b] = r.last_dec;
     }
     if (smooth) sm_clock.read(c, nsmooth);
+    if (bw) {
+        sm_clock.elapsed(c->ssm_bw_us);
+        c->ssm_bw_bytes = (int64_t)nbw;
+    }
     c->ssm_batch_per_cu = per_cu;
     c->ssm_batch_cus = cus;
     c->ssm_batch_segments = nseg;
     c->ssm_batch_wall_us = us(t_in, clk::now());
+    if (bw_flag) return fail(WSMC_ESTATE, "ssm batch backward: exp_norm of the weights is NaN at some step of some trajectory (the filters themselves are complete)");
     return WSMC_OK;
 }
 
@@ -6286,6 +6651,15 @@ int wsmc_ssm_run_batch_smoothed(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t
                                 wsmc_ssm_batch_out* out, const wsmc_ssm_trace* trace, const wsmc_ssm_smooth* smooth) {
     return ssm_run_batch(c, specs, n_specs, data, n_tables, T, n, B, seeds, ess_min, scheme, out, trace ? *trace : kNoTrace,
                          smooth ? *smooth : kNoSmooth);
+}
+
+int wsmc_ssm_run_batch_backward(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_specs, const double* data, int32_t n_tables,
+                                int32_t T, int32_t n, int32_t B, const uint64_t* seeds, double ess_min, int32_t scheme,
+                                wsmc_ssm_batch_out* out, const wsmc_ssm_trace* trace, int32_t M, const uint64_t* bw_seeds,
+                                const wsmc_ssm_backward_out* bw_out) {
+    if (!bw_out) return fail(WSMC_EARG, "ssm batch backward: null bw_out");
+    return ssm_run_batch(c, specs, n_specs, data, n_tables, T, n, B, seeds, ess_min, scheme, out, trace ? *trace : kNoTrace, kNoSmooth, M,
+                         bw_seeds, bw_out);
 }
 
 int wsmc_debug_ssm_smooth(wsmc_ctx* c, int64_t* stats_out) {

@@ -395,6 +395,9 @@ struct wsmc_ctx {
     // the last smoothed run or batch (wsmc_debug_ssm_smooth): device microseconds of the segments,
     // the trace-back and the rows kernel, and the bytes of the log
     int64_t ssm_smooth_us[3] = {0, 0, 0}, ssm_smooth_bytes = 0;
+    // the last backward pass (wsmc_debug_ssm_backward): the segments, the backward kernel, the rows kernel; its bytes
+    int64_t ssm_bw_us[3] = {0, 0, 0}, ssm_bw_bytes = 0;
+    int64_t ssm_bw_launches = 0;            // segments launched on the backward-recording kernels (cumulative)
     bool timing = false;
     std::vector<hipEvent_t> events;
     wsmc_run_timing last_timing{};
@@ -1011,6 +1014,56 @@ struct SsmGuidedArgs {        // both guided single-run kernels (r: the recordin
     const SsmTarget* targ;    // [kSsmTargets]
 };
 static_assert(sizeof(SsmGuidedArgs) + 32 <= 4096, "the spec rides in the kernel arguments");
+// A run that ends in backward simulation (wsmc_ssm_run_backward): what its recording kernels
+// (csrc/wsmc_ssm_backward_rec.hip, csrc/wsmc_ssm_guided_backward_rec.hip) log at every trace point:
+// the columns, as a smoothed run's, and the log-weights beside them. No ancestor log. Kernels of
+// names and arguments of their own, so every other entry point launches what it launched before.
+struct SsmBwRec {
+    double* hist;             // [T][S][N]
+    double* lwlog;            // [T][N]
+    int32_t T, pad;
+};
+struct SsmBwRecArgs {
+    SsmArgs a;
+    SsmBwRec r;
+};
+static_assert(sizeof(SsmBwRecArgs) + 32 <= 4096, "the spec rides in the kernel arguments");
+struct SsmGuidedBwArgs {
+    SsmBwRecArgs ra;
+    const SsmTarget* targ;    // [kSsmTargets]
+};
+static_assert(sizeof(SsmGuidedBwArgs) + 32 <= 4096, "the spec rides in the kernel arguments");
+hipError_t launch_ssm_segment_bwrec(hipStream_t s, const SsmBwRecArgs& a, unsigned feat, int threads);
+hipError_t launch_ssm_guided_segment_bwrec(hipStream_t s, const SsmGuidedBwArgs& a, unsigned feat, int threads);
+// The backward pass (csrc/wsmc_ssm_backward.hip, wsmc_ssm_backward): one workgroup a (filter,
+// trajectory), t looped on the device from T - 1 down to 0. A filter's step is read from device
+// memory at a block-uniform address (scalar loads), as the batch kernel reads its SsmBatchFilter.
+struct SsmBwFilter {
+    SsmStmt step[WSMC_SSM_MAX_STMTS];      // prog: offsets into ins
+    SsmTarget targ[WSMC_SSM_MAX_STMTS];    // an importance SAMPLE's target, at its statement's index
+    SsmIns ins[kSsmProgMax];
+    int32_t included[WSMC_SSM_MAX_STMTS];  // wsmc_ssm_spec_backward's
+    uint64_t seed;                         // the draws' (word (seed, t M + m, 0))
+    const double* data;                    // [T x data_dim]
+};
+struct SsmBwArgs {
+    const double* hist;       // [B][T][S][N] the record's columns
+    const double* lwlog;      // [B][T][N] ... and log-weights
+    int32_t* idx;             // [B][T][M] out
+    int32_t* flag;            // [1] set when a draw met Q == 0 (exp_norm of the weights is NaN)
+    const SsmBwFilter* filt;  // [B]
+    int32_t N, P;             // particles, particles per thread
+    int32_t S, data_dim;
+    int32_t T, M;
+    int32_t n_step, B;
+};
+hipError_t launch_ssm_backward(hipStream_t s, const SsmBwArgs& a, unsigned feat, int threads);
+int ssm_backward_threads(int n);
+// one workgroup a (filter, step): row t of paths [B][T][S][M] gathered from hist through idx, and
+// wsmc_weighted_moments of it on M particles with zero log-weights (ss_trace_row's canonical sums).
+// paths / mean / var: null when not wanted
+hipError_t launch_ssm_backward_rows(hipStream_t s, const double* hist, const int32_t* idx, double* paths, double* mean,
+                                    double* var, int N, int M, int S, int T, int B);
 size_t ssm_lds_bytes(int n, int S);
 // feat: WSMC_FEAT_EXT / WSMC_FEAT_GAM bits over the spec's dists (the kernel's instantiation)
 int ssm_threads(unsigned feat, int n);
@@ -1080,11 +1133,23 @@ struct SsmBatchGuidedArgs {   // both guided batch kernels (see SsmGuidedArgs)
     const SsmTarget* targ;    // [B][kSsmTargets]
 };
 // blocks of the variant that are resident on one CU (by registers, waves and LDS), and the device's CUs.
-// variant: 0 untraced, 1 traced, 2 recording, 3 guided, 4 guided recording
+// variant: 0 untraced, 1 traced, 2 recording, 3 guided, 4 guided recording, 5 backward recording, 6 guided backward recording
 hipError_t ssm_batch_occupancy(int device, unsigned feat, int variant, int threads, size_t lds, int* per_cu, int* cus);
 hipError_t launch_ssm_batch_segment(hipStream_t s, const SsmBatchArgs& a, unsigned feat, int threads);
 hipError_t launch_ssm_batch_segment_rec(hipStream_t s, const SsmBatchRecArgs& a, unsigned feat, int threads);
 hipError_t launch_ssm_batch_guided_segment(hipStream_t s, const SsmBatchGuidedArgs& a, unsigned feat, int threads, bool rec);
+// a batch that ends in backward simulation (wsmc_ssm_run_batch_backward; csrc/wsmc_ssm_batch_backward_rec.hip,
+// csrc/wsmc_ssm_batch_guided_backward_rec.hip): SsmBwRec's arrays are [B]-leading, filter b's rows at b * T
+struct SsmBatchBwRecArgs {
+    SsmBatchArgs a;
+    SsmBwRec r;
+};
+struct SsmBatchGuidedBwArgs {
+    SsmBatchBwRecArgs ra;
+    const SsmTarget* targ;    // [B][kSsmTargets]
+};
+hipError_t launch_ssm_batch_segment_bwrec(hipStream_t s, const SsmBatchBwRecArgs& a, unsigned feat, int threads);
+hipError_t launch_ssm_batch_guided_segment_bwrec(hipStream_t s, const SsmBatchGuidedBwArgs& a, unsigned feat, int threads);
 // one handle over several devices (wsmc_multi.hip): the ABI entry points fan out
 int multi_destroy(wsmc_ctx* c);
 wsmc_ctx* multi_first(wsmc_ctx* c);

@@ -41,20 +41,34 @@ namespace wsmc {
 // untraced call) whose statement body also holds k_sample_importance's arithmetic, and their
 // recording twins. Kernels of other names again, so a spec without the new kinds launches what it
 // always has.
+// A sixth and a seventh time through csrc/wsmc_ssm_backward_rec.hip (WSMC_SSM_BWREC) and
+// csrc/wsmc_ssm_guided_backward_rec.hip (with WSMC_SSM_GUIDED) for a run that ends in backward
+// simulation (wsmc_ssm_run_backward): traced instantiations that log the trace point's columns and
+// log-weights (SsmBwRec) and no ancestors. Kernels of other names once more.
 #if defined(WSMC_SSM_GUIDED)
 constexpr bool kSsTraced = true, kSsGuided = true;
-#if defined(WSMC_SSM_SMOOTH)
+#if defined(WSMC_SSM_BWREC)
+#define WSMC_SSM_VARIANTS ssm_launch_guided_bwrec
+#define WSMC_SSM_KERNEL k_ssm_guided_segment_bwrec
+typedef SsmGuidedBwArgs SsKernArgs;
+#elif defined(WSMC_SSM_SMOOTH)
 #define WSMC_SSM_VARIANTS ssm_launch_guided_rec
 #define WSMC_SSM_KERNEL k_ssm_guided_segment_rec
+typedef SsmGuidedArgs SsKernArgs;
 #else
 #define WSMC_SSM_VARIANTS ssm_launch_guided
 #define WSMC_SSM_KERNEL k_ssm_guided_segment
-#endif
 typedef SsmGuidedArgs SsKernArgs;
+#endif
 namespace {
 constexpr int kSsVariantGamThreads = kSsGuidedGamThreads;
 typedef const SsmTarget __attribute__((address_space(4))) * SsTargetPtr;
 }
+#elif defined(WSMC_SSM_BWREC)
+constexpr bool kSsTraced = true;
+#define WSMC_SSM_VARIANTS ssm_launch_bwrec
+#define WSMC_SSM_KERNEL k_ssm_segment_bwrec
+typedef SsmBwRecArgs SsKernArgs;
 #elif defined(WSMC_SSM_SMOOTH)
 constexpr bool kSsTraced = true;
 #define WSMC_SSM_VARIANTS ssm_launch_rec
@@ -93,12 +107,16 @@ __global__ __launch_bounds__(THREADS) void WSMC_SSM_KERNEL(SsKernArgs) {
     static_assert(offsetof(SsmRecArgs, a) == 0, "the run's arguments come first");
     const SsmRec& rc = *(const SsmRec*)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(SsmRecArgs, r));
 #endif
+#ifdef WSMC_SSM_BWREC
+    static_assert(offsetof(SsmBwRecArgs, a) == 0, "the run's arguments come first");
+    const SsmBwRec& rc = *(const SsmBwRec*)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(SsmBwRecArgs, r));
+#endif
 #ifdef WSMC_SSM_GUIDED
-    static_assert(offsetof(SsmGuidedArgs, ra) == 0, "the run's arguments come first");
+    static_assert(offsetof(SsKernArgs, ra) == 0, "the run's arguments come first");
     // the targets: written before the run's first launch and by nothing while a kernel runs; a
     // uniform address, so the loads are scalar (as the batch kernel reads its SsmBatchFilter)
     const SsmTarget* const tgs = (const SsmTarget*)(SsTargetPtr)(
-        *(const SsmTarget* const*)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(SsmGuidedArgs, targ)));
+        *(const SsmTarget* const*)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(SsKernArgs, targ)));
 #endif
     extern __shared__ __attribute__((aligned(16))) char ss_smem[];
     const int tid = (int)threadIdx.x, nthr = (int)blockDim.x;
@@ -169,8 +187,11 @@ __global__ __launch_bounds__(THREADS) void WSMC_SSM_KERNEL(SsKernArgs) {
                        (kSsGuided && (st.kind == WSMC_SSM_WEIGHT || st.kind == WSMC_SSM_SAMPLE_IMPORTANCE))) {
                 if (kSsGuided && st.kind == WSMC_SSM_SAMPLE_IMPORTANCE) op += 1;   // its draws took `op`; its Resample can run
                 const bool row = TR && !init && q == a.last_obs;
-#ifdef WSMC_SSM_SMOOTH
+#if defined(WSMC_SSM_SMOOTH) || defined(WSMC_SSM_BWREC)
                 if (row) ss_record_cols(L, rc.hist + (size_t)t * S * N);
+#endif
+#ifdef WSMC_SSM_BWREC
+                if (row) ss_record_lw(L, rc.lwlog + (size_t)t * N);
 #endif
                 if (row && (a.tr_mean || a.tr_var))
                     ss_trace_row(L, a.tr_mean ? a.tr_mean + (size_t)t * S : nullptr, a.tr_var ? a.tr_var + (size_t)t * S : nullptr);
@@ -220,7 +241,7 @@ hipError_t WSMC_SSM_VARIANTS(hipStream_t s, const SsKernArgs& a, unsigned feat, 
     return ssm_launch<0u, kSsMaxThreads>(s, a, threads, lds);
 }
 
-#if !defined(WSMC_SSM_TRACED) && !defined(WSMC_SSM_SMOOTH) && !defined(WSMC_SSM_GUIDED)
+#if !defined(WSMC_SSM_TRACED) && !defined(WSMC_SSM_SMOOTH) && !defined(WSMC_SSM_GUIDED) && !defined(WSMC_SSM_BWREC)
 int ssm_threads(unsigned feat, int n) {
     const int cap = (feat & WSMC_FEAT_GAM) ? kSsGamThreads : kSsMaxThreads;
     // two particles a thread where the workgroup allows (wsmc_lgssm1d_run's measured choice)
@@ -261,6 +282,21 @@ hipError_t launch_ssm_guided_segment(hipStream_t s, const SsmGuidedArgs& a, unsi
         return hipErrorInvalidValue;
     const size_t lds = ssm_lds_bytes(ra.N, ra.S);
     return rec ? ssm_launch_guided_rec(s, a, feat, threads, lds) : ssm_launch_guided(s, a, feat, threads, lds);
+}
+
+hipError_t ssm_launch_bwrec(hipStream_t s, const SsmBwRecArgs& a, unsigned feat, int threads, size_t lds);             // csrc/wsmc_ssm_backward_rec.hip
+hipError_t ssm_launch_guided_bwrec(hipStream_t s, const SsmGuidedBwArgs& a, unsigned feat, int threads, size_t lds);   // csrc/wsmc_ssm_guided_backward_rec.hip
+
+hipError_t launch_ssm_segment_bwrec(hipStream_t s, const SsmBwRecArgs& a, unsigned feat, int threads) {
+    if (!ss_segment_ok(a.a, feat, threads) || !a.r.hist || !a.r.lwlog || a.a.t0 + a.a.nsteps > a.r.T) return hipErrorInvalidValue;
+    return ssm_launch_bwrec(s, a, feat, threads, ssm_lds_bytes(a.a.N, a.a.S));
+}
+
+hipError_t launch_ssm_guided_segment_bwrec(hipStream_t s, const SsmGuidedBwArgs& a, unsigned feat, int threads) {
+    const SsmArgs& ra = a.ra.a;
+    if (!ss_segment_ok(ra, feat, threads, true) || !a.targ || !a.ra.r.hist || !a.ra.r.lwlog || ra.t0 + ra.nsteps > a.ra.r.T)
+        return hipErrorInvalidValue;
+    return ssm_launch_guided_bwrec(s, a, feat, threads, ssm_lds_bytes(ra.N, ra.S));
 }
 #endif
 

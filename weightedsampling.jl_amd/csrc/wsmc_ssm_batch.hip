@@ -28,22 +28,37 @@ namespace wsmc {
 // and through csrc/wsmc_ssm_batch_guided.hip (WSMC_SSM_GUIDED) and
 // csrc/wsmc_ssm_batch_guided_smooth.hip (both macros) for the kernels of a guided spec's batch, as
 // in csrc/wsmc_ssm.hip
+// and through csrc/wsmc_ssm_batch_backward_rec.hip (WSMC_SSM_BWREC) and
+// csrc/wsmc_ssm_batch_guided_backward_rec.hip (with WSMC_SSM_GUIDED) for a batch that ends in backward
+// simulation: the trace point's columns and log-weights logged, no ancestors, as in csrc/wsmc_ssm.hip
 #if defined(WSMC_SSM_GUIDED)
 constexpr bool kSsbTraced = true, kSsbGuided = true;
-#if defined(WSMC_SSM_SMOOTH)
+#if defined(WSMC_SSM_BWREC)
+#define WSMC_SSB_OCCUPANCY ssb_occupancy_guided_bwrec
+#define WSMC_SSB_VARIANTS ssb_launch_guided_bwrec
+#define WSMC_SSB_KERNEL k_ssm_batch_guided_segment_bwrec
+typedef SsmBatchGuidedBwArgs SsbKernArgs;
+#elif defined(WSMC_SSM_SMOOTH)
 #define WSMC_SSB_OCCUPANCY ssb_occupancy_guided_rec
 #define WSMC_SSB_VARIANTS ssb_launch_guided_rec
 #define WSMC_SSB_KERNEL k_ssm_batch_guided_segment_rec
+typedef SsmBatchGuidedArgs SsbKernArgs;
 #else
 #define WSMC_SSB_OCCUPANCY ssb_occupancy_guided
 #define WSMC_SSB_VARIANTS ssb_launch_guided
 #define WSMC_SSB_KERNEL k_ssm_batch_guided_segment
-#endif
 typedef SsmBatchGuidedArgs SsbKernArgs;
+#endif
 namespace {
 constexpr int kSsbVariantGamThreads = kSsGuidedGamThreads;
 typedef const SsmTarget __attribute__((address_space(4))) * SsTargetPtr;
 }
+#elif defined(WSMC_SSM_BWREC)
+constexpr bool kSsbTraced = true;
+#define WSMC_SSB_OCCUPANCY ssb_occupancy_bwrec
+#define WSMC_SSB_VARIANTS ssb_launch_bwrec
+#define WSMC_SSB_KERNEL k_ssm_batch_segment_bwrec
+typedef SsmBatchBwRecArgs SsbKernArgs;
 #elif defined(WSMC_SSM_SMOOTH)
 constexpr bool kSsbTraced = true;
 #define WSMC_SSB_OCCUPANCY ssb_occupancy_rec
@@ -74,9 +89,16 @@ constexpr int kSsbVariantGamThreads = kSsGamThreads;
 
 // TR: the traced batch (wsmc_ssm_run_batch_traced), k_ssm_segment's flag
 template <unsigned FEAT, int THREADS, bool TR>
-#if defined(WSMC_SSM_GUIDED)
+#if defined(WSMC_SSM_GUIDED) && defined(WSMC_SSM_BWREC)
+__global__ __launch_bounds__(THREADS) void WSMC_SSB_KERNEL(const SsmBatchGuidedBwArgs ga) {
+    const SsmBatchBwRecArgs& ka = ga.ra;
+    const SsmBatchArgs& a = ka.a;
+#elif defined(WSMC_SSM_GUIDED)
 __global__ __launch_bounds__(THREADS) void WSMC_SSB_KERNEL(const SsmBatchGuidedArgs ga) {
     const SsmBatchRecArgs& ka = ga.ra;
+    const SsmBatchArgs& a = ka.a;
+#elif defined(WSMC_SSM_BWREC)
+__global__ __launch_bounds__(THREADS) void WSMC_SSB_KERNEL(const SsmBatchBwRecArgs ka) {
     const SsmBatchArgs& a = ka.a;
 #elif defined(WSMC_SSM_SMOOTH)
 __global__ __launch_bounds__(THREADS) void WSMC_SSB_KERNEL(const SsmBatchRecArgs ka) {
@@ -92,6 +114,11 @@ __global__ __launch_bounds__(THREADS) void WSMC_SSB_KERNEL(const SsmBatchArgs a)
     double* hist = ka.r.hist + b * (size_t)ka.r.T * (size_t)a.S * (size_t)a.N;
     int32_t* alog = ka.r.alog + b * (size_t)ka.r.T * (size_t)ka.r.n_slots * (size_t)a.N;
     int32_t* ranf = ka.r.ran + b * (size_t)ka.r.T * (size_t)ka.r.n_slots;
+#endif
+#ifdef WSMC_SSM_BWREC
+    // filter b's rows of the record
+    double* hist = ka.r.hist + b * (size_t)ka.r.T * (size_t)a.S * (size_t)a.N;
+    double* lwlog = ka.r.lwlog + b * (size_t)ka.r.T * (size_t)a.N;
 #endif
 #ifdef WSMC_SSM_GUIDED
     // filter b's targets (block-uniform: scalar loads, as its statements' below)
@@ -171,8 +198,11 @@ __global__ __launch_bounds__(THREADS) void WSMC_SSB_KERNEL(const SsmBatchArgs a)
                 if (kSsbGuided && st.kind == WSMC_SSM_SAMPLE_IMPORTANCE) op += 1;   // its draws took `op`; its Resample can run
                 const bool row = TR && !init && q == a.last_obs;
                 const size_t r = b * (size_t)a.T + (size_t)t;
-#ifdef WSMC_SSM_SMOOTH
+#if defined(WSMC_SSM_SMOOTH) || defined(WSMC_SSM_BWREC)
                 if (row) ss_record_cols(L, hist + (size_t)t * S * N);
+#endif
+#ifdef WSMC_SSM_BWREC
+                if (row) ss_record_lw(L, lwlog + (size_t)t * N);
 #endif
                 if (row && (a.tr_mean || a.tr_var))
                     ss_trace_row(L, a.tr_mean ? a.tr_mean + r * S : nullptr, a.tr_var ? a.tr_var + r * S : nullptr);
@@ -285,7 +315,11 @@ hipError_t WSMC_SSB_VARIANTS(hipStream_t s, const SsbKernArgs& a, unsigned feat,
     return ssb_launch<0u, kSsMaxThreads>(s, a, threads, lds, B);
 }
 
-#if !defined(WSMC_SSM_TRACED) && !defined(WSMC_SSM_SMOOTH) && !defined(WSMC_SSM_GUIDED)
+#if !defined(WSMC_SSM_TRACED) && !defined(WSMC_SSM_SMOOTH) && !defined(WSMC_SSM_GUIDED) && !defined(WSMC_SSM_BWREC)
+hipError_t ssb_occupancy_bwrec(unsigned feat, int threads, size_t lds, int* per_cu);          // csrc/wsmc_ssm_batch_backward_rec.hip
+hipError_t ssb_launch_bwrec(hipStream_t s, const SsmBatchBwRecArgs& a, unsigned feat, int threads, size_t lds, int B);
+hipError_t ssb_occupancy_guided_bwrec(unsigned feat, int threads, size_t lds, int* per_cu);   // csrc/wsmc_ssm_batch_guided_backward_rec.hip
+hipError_t ssb_launch_guided_bwrec(hipStream_t s, const SsmBatchGuidedBwArgs& a, unsigned feat, int threads, size_t lds, int B);
 hipError_t ssb_occupancy_guided(unsigned feat, int threads, size_t lds, int* per_cu);       // csrc/wsmc_ssm_batch_guided.hip
 hipError_t ssb_launch_guided(hipStream_t s, const SsmBatchGuidedArgs& a, unsigned feat, int threads, size_t lds, int B);
 hipError_t ssb_occupancy_guided_rec(unsigned feat, int threads, size_t lds, int* per_cu);   // csrc/wsmc_ssm_batch_guided_smooth.hip
@@ -298,6 +332,8 @@ hipError_t ssb_launch_rec(hipStream_t s, const SsmBatchRecArgs& a, unsigned feat
 hipError_t ssm_batch_occupancy(int device, unsigned feat, int variant, int threads, size_t lds, int* per_cu, int* cus) {
     const hipError_t e = hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, device);
     if (e != hipSuccess) return e;
+    if (variant == 6) return ssb_occupancy_guided_bwrec(feat, threads, lds, per_cu);
+    if (variant == 5) return ssb_occupancy_bwrec(feat, threads, lds, per_cu);
     if (variant == 4) return ssb_occupancy_guided_rec(feat, threads, lds, per_cu);
     if (variant == 3) return ssb_occupancy_guided(feat, threads, lds, per_cu);
     if (variant == 2) return ssb_occupancy_rec(feat, threads, lds, per_cu);
@@ -329,6 +365,17 @@ hipError_t launch_ssm_batch_guided_segment(hipStream_t s, const SsmBatchGuidedAr
         return hipErrorInvalidValue;
     const size_t lds = ssm_lds_bytes(ba.N, ba.S);
     return rec ? ssb_launch_guided_rec(s, a, feat, threads, lds, ba.B) : ssb_launch_guided(s, a, feat, threads, lds, ba.B);
+}
+
+hipError_t launch_ssm_batch_segment_bwrec(hipStream_t s, const SsmBatchBwRecArgs& a, unsigned feat, int threads) {
+    if (!ssb_segment_ok(a.a, feat, threads) || !a.r.hist || !a.r.lwlog || a.r.T != a.a.T) return hipErrorInvalidValue;
+    return ssb_launch_bwrec(s, a, feat, threads, ssm_lds_bytes(a.a.N, a.a.S), a.a.B);
+}
+
+hipError_t launch_ssm_batch_guided_segment_bwrec(hipStream_t s, const SsmBatchGuidedBwArgs& a, unsigned feat, int threads) {
+    const SsmBatchArgs& ba = a.ra.a;
+    if (!ssb_segment_ok(ba, feat, threads, true) || !a.targ || !a.ra.r.hist || !a.ra.r.lwlog || a.ra.r.T != ba.T) return hipErrorInvalidValue;
+    return ssb_launch_guided_bwrec(s, a, feat, threads, ssm_lds_bytes(ba.N, ba.S), ba.B);
 }
 #endif
 

@@ -495,6 +495,11 @@ __device__ inline void ss_record_cols(const SsState& L, double* hist) {
         for (int i = L.i0; i < L.i1; ++i) dst[i] = src[i];
     }
 }
+// (wsmc_ssm_run_backward's recording units) the trace point's log-weights to row t of their log,
+// beside the columns: lwlog: the row's [N] doubles in global memory
+__device__ inline void ss_record_lw(const SsState& L, double* lwlog) {
+    for (int i = L.i0; i < L.i1; ++i) lwlog[i] = L.lw[i];
+}
 // After a Resample that ran: its ancestors (each written by its particle's owner in ss_resample)
 // to the slot's [N] row of the log, and the slot's flag
 __device__ inline void ss_record_anc(const SsState& L, int32_t* slot, int32_t* ran) {

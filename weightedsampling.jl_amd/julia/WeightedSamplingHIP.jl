@@ -1058,4 +1058,135 @@ function ssm_run_batch_smoothed(state::HipState, specs, data, n::Integer, seeds:
     return (log_evidence=ev, n_resamples=nres, last_resampled=last .!= 0, smean=mean, svar=var, paths=pa, log_weights=lw)
 end
 
+# ---- backward simulation (include/wsmc.h wsmc_ssm_backward). Written against the C ABI; not run in
+# this repository's checks, which have no Julia.
+# wsmc_ssm_backward_out: host buffers of a backward pass, C_NULL for the ones not wanted
+struct WsmcSsmBackwardOut
+    idx::Ptr{Int32}
+    paths::Ptr{Float64}
+    mean::Ptr{Float64}
+    var::Ptr{Float64}
+    particles::Ptr{Float64}
+    log_weights::Ptr{Float64}
+end
+
+"""
+    ssm_spec_backward(spec) -> Vector{Int}
+
+The statements of `spec`'s step (1-based) whose log-density enters the backward weight of forward
+filtering, backward simulation (`wsmc_ssm_spec_backward`); throws with the library's reason for a
+spec backward simulation is not defined for (a statement after the last observe, a column sampled
+and assigned, a static parameter or any deterministic carry-over of the state).
+"""
+function ssm_spec_backward(spec::WsmcSsmSpec)
+    inc = zeros(Int32, 8)   # WSMC_SSM_MAX_STMTS
+    check(ccall((:wsmc_ssm_spec_backward, libwsmc), Cint, (Ref{WsmcSsmSpec}, Ptr{Int32}), spec, inc))
+    return findall(!=(0), inc)
+end
+
+_bw_buffers(T, S, n, M, lead...) = (idx=Array{Int32}(undef, M, T, lead...), paths=Array{Float64}(undef, M, S, T, lead...),
+                                    mean=Array{Float64}(undef, S, T, lead...), var=Array{Float64}(undef, S, T, lead...))
+
+"""
+    ssm_backward(state, spec, data, particles, log_weights, M, seed) -> (idx, paths, mean, var)
+
+M trajectories drawn backwards through a record the caller holds (`wsmc_ssm_backward`): `particles`
+n x n_cols x T and `log_weights` n x T at the trace points of a run of `spec` over `data`. `idx`
+(M x T, 0-based particle indices), `paths` (M x n_cols x T), `mean` and `var` (n_cols x T) over the M
+equal-weight trajectories. `state` gives the device and the stream only. An auxiliary column
+assigned from the old state holds the filter particle's own value, not f of the drawn state.
+"""
+function ssm_backward(state::HipState, spec::WsmcSsmSpec, data::AbstractVecOrMat, particles::Array{Float64,3},
+                      log_weights::Matrix{Float64}, M::Integer, seed::Integer)
+    n, S, T = size(particles)
+    size(log_weights) == (n, T) && S == Int(spec.n_cols) && size(data, 1) == T || throw(ArgumentError("the record's shape"))
+    d = Vector{Float64}(vec(permutedims(reshape(Float64.(data), T, :))))
+    b = _bw_buffers(T, S, n, M)
+    GC.@preserve b particles log_weights begin
+        out = WsmcSsmBackwardOut(pointer(b.idx), pointer(b.paths), pointer(b.mean), pointer(b.var), C_NULL, C_NULL)
+        check(ccall((:wsmc_ssm_backward, libwsmc), Cint,
+                    (Ptr{Cvoid}, Ref{WsmcSsmSpec}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Int32, UInt64,
+                     Ref{WsmcSsmBackwardOut}),
+                    state.store.ctx, spec, isempty(d) ? C_NULL : d, T, particles, log_weights, n, M, seed % UInt64, out))
+    end
+    return b
+end
+
+"""
+    ssm_run_backward!(state, spec, data, M, seed; scheme, record=false) -> (log_evidence, backward)
+
+`ssm_run!` followed on the device by the backward pass over the run's own record
+(`wsmc_ssm_run_backward`): `backward` is `ssm_backward`'s tuple, with `particles` (n x n_cols x T) and
+`log_weights` (n x T) when `record`. Everything the run leaves on `state` is `ssm_run_traced!`'s; the
+draws come from `seed`, not from the state's stream. The persistent route only.
+"""
+function ssm_run_backward!(state::HipState, spec::WsmcSsmSpec, data::AbstractVecOrMat, M::Integer, seed::Integer;
+                           scheme=RESAMPLE_STRATIFIED, record::Bool=false)
+    T = size(data, 1)
+    S = Int(spec.n_cols)
+    n = Ref{Int64}(0)
+    check(ccall((:wsmc_nparticles, libwsmc), Cint, (Ptr{Cvoid}, Ref{Int64}), state.store.ctx, n))
+    d = Vector{Float64}(vec(permutedims(reshape(Float64.(data), T, :))))
+    ev = Ref{Float64}(0.0)
+    b = _bw_buffers(T, S, n[], M)
+    pa = record ? Array{Float64}(undef, n[], S, T) : nothing
+    lw = record ? Matrix{Float64}(undef, n[], T) : nothing
+    GC.@preserve b pa lw begin
+        out = WsmcSsmBackwardOut(pointer(b.idx), pointer(b.paths), pointer(b.mean), pointer(b.var),
+                                 pa === nothing ? C_NULL : pointer(pa), lw === nothing ? C_NULL : pointer(lw))
+        check(ccall((:wsmc_ssm_run_backward, libwsmc), Cint,
+                    (Ptr{Cvoid}, Ref{WsmcSsmSpec}, Ptr{Float64}, Int32, Float64, Int32, Ptr{Float64}, Ptr{Cvoid}, Int32, UInt64,
+                     Ref{WsmcSsmBackwardOut}),
+                    state.store.ctx, spec, isempty(d) ? C_NULL : d, T, state.ess_perc_min, scheme, ev, C_NULL, M, seed % UInt64, out))
+    end
+    mirror_flags!(state)
+    return ev[], (; b..., particles=pa, log_weights=lw)
+end
+
+"""
+    ssm_run_batch_backward(state, specs, data, n, seeds, M, bw_seeds; scheme)
+
+`ssm_run_batch` with every filter's backward pass (`wsmc_ssm_run_batch_backward`): the named tuple also
+holds `idx` (M x T x B), `paths` (M x n_cols x T x B), `mean` and `var` (n_cols x T x B); filter b is
+`ssm_run_backward!` on a fresh state of seed `seeds[b]` with `bw_seeds[b]`.
+"""
+function ssm_run_batch_backward(state::HipState, specs, data, n::Integer, seeds::AbstractVector{<:Integer}, M::Integer,
+                                bw_seeds::AbstractVector{<:Integer}; scheme=RESAMPLE_STRATIFIED)
+    B = length(seeds)
+    length(bw_seeds) == B || throw(ArgumentError("one backward seed per filter"))
+    sp = specs isa WsmcSsmSpec ? [specs] : collect(WsmcSsmSpec, specs)
+    tabs = data isa AbstractVector{<:AbstractVecOrMat} ? collect(data) : [data]
+    length(sp) in (1, B) && length(tabs) in (1, B) || throw(ArgumentError("one spec / table, or one per filter"))
+    T = size(tabs[1], 1)
+    all(t -> size(t, 1) == T, tabs) || throw(ArgumentError("the filters' tables must have one length"))
+    rowmajor(t) = Vector{Float64}(vec(permutedims(reshape(Float64.(t), T, :))))
+    d = reduce(vcat, rowmajor.(tabs))
+    S = Int(sp[1].n_cols)
+    ev = Vector{Float64}(undef, B); nres = Vector{Int64}(undef, B); last = Vector{Int32}(undef, B)
+    b = _bw_buffers(T, S, n, M, B)
+    sd = Vector{UInt64}(seeds .% UInt64); bsd = Vector{UInt64}(bw_seeds .% UInt64)
+    GC.@preserve ev nres last b begin
+        out = WsmcSsmBatchOut(pointer(ev), C_NULL, C_NULL, C_NULL, C_NULL, pointer(nres), pointer(last))
+        bo = WsmcSsmBackwardOut(pointer(b.idx), pointer(b.paths), pointer(b.mean), pointer(b.var), C_NULL, C_NULL)
+        check(ccall((:wsmc_ssm_run_batch_backward, libwsmc), Cint,
+                    (Ptr{Cvoid}, Ptr{WsmcSsmSpec}, Int32, Ptr{Float64}, Int32, Int32, Int32, Int32, Ptr{UInt64},
+                     Float64, Int32, Ref{WsmcSsmBatchOut}, Ptr{Cvoid}, Int32, Ptr{UInt64}, Ref{WsmcSsmBackwardOut}),
+                    state.store.ctx, sp, length(sp), isempty(d) ? C_NULL : d, length(tabs), T, n, B, sd,
+                    state.ess_perc_min, scheme, out, C_NULL, M, bsd, bo))
+    end
+    return (; log_evidence=ev, n_resamples=nres, last_resampled=last .!= 0, b...)
+end
+
+"""
+    debug_ssm_backward(state)
+
+`wsmc_debug_ssm_backward`: the last backward pass's device microseconds (the run's segments, the
+backward kernel, the rows kernel), its bytes, and the segments launched on the recording kernels.
+"""
+function debug_ssm_backward(state::HipState)
+    st = zeros(Int64, 5)
+    check(ccall((:wsmc_debug_ssm_backward, libwsmc), Cint, (Ptr{Cvoid}, Ptr{Int64}), state.store.ctx, st))
+    return (segments_us=st[1], backward_us=st[2], rows_us=st[3], bytes=st[4], recording_segments=st[5])
+end
+
 end # module

@@ -130,6 +130,12 @@ class SsmSmoothOut(C.Structure):
     _fields_ = [("paths", C.POINTER(C.c_double)), ("mean", C.POINTER(C.c_double)), ("var", C.POINTER(C.c_double))]
 
 
+class SsmBackwardOut(C.Structure):
+    """wsmc_ssm_backward_out: caller-owned host buffers of a backward-simulation pass (NULL: not wanted)"""
+    _fields_ = [("idx", C.POINTER(C.c_int32)), ("paths", C.POINTER(C.c_double)), ("mean", C.POINTER(C.c_double)),
+                ("var", C.POINTER(C.c_double)), ("particles", C.POINTER(C.c_double)), ("log_weights", C.POINTER(C.c_double))]
+
+
 class RunTiming(C.Structure):
     _fields_ = [("total_ms", C.c_double), ("propagate_ms", C.c_double),
                 ("reduce_ms", C.c_double), ("resample_ms", C.c_double),
@@ -222,6 +228,16 @@ SIGNATURES = {
     "wsmc_ssm_run_batch_smoothed": (C.c_int, [_P, C.POINTER(SsmSpec), C.c_int32, _D, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                               C.POINTER(C.c_uint64), C.c_double, C.c_int32, C.POINTER(SsmBatchOut),
                                               C.POINTER(SsmTraceOut), C.POINTER(SsmSmoothOut)]),
+    "wsmc_ssm_spec_backward": (C.c_int, [C.POINTER(SsmSpec), _I32P]),
+    "wsmc_ssm_backward_out_sizeof": (C.c_int, [C.POINTER(C.c_int64)]),
+    "wsmc_ssm_backward": (C.c_int, [_P, C.POINTER(SsmSpec), _D, C.c_int32, _D, _D, C.c_int32, C.c_int32, C.c_uint64,
+                                    C.POINTER(SsmBackwardOut)]),
+    "wsmc_ssm_run_backward": (C.c_int, [_P, C.POINTER(SsmSpec), _D, C.c_int32, C.c_double, C.c_int32, _D,
+                                        C.POINTER(SsmTraceOut), C.c_int32, C.c_uint64, C.POINTER(SsmBackwardOut)]),
+    "wsmc_ssm_run_batch_backward": (C.c_int, [_P, C.POINTER(SsmSpec), C.c_int32, _D, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                              C.POINTER(C.c_uint64), C.c_double, C.c_int32, C.POINTER(SsmBatchOut),
+                                              C.POINTER(SsmTraceOut), C.c_int32, C.POINTER(C.c_uint64), C.POINTER(SsmBackwardOut)]),
+    "wsmc_debug_ssm_backward": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "wsmc_run_set_timing": (C.c_int, [_P, C.c_int32]),
     "wsmc_run_get_timing": (C.c_int, [_P, C.POINTER(RunTiming)]),
     "wsmc_debug_kernel_bench": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _D]),

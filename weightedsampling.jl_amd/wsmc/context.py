@@ -15,8 +15,8 @@ import numpy as np
 
 from . import abi
 from .abi import Dist, Operand, RunTiming, State, check, load_library
-from .ssm import (TRACE_PARTS, SsmSmooth, SsmTrace, batch_arguments, smooth_buffers, smooth_by_name, smooth_parts, trace_buffers,
-                  trace_by_name, trace_parts)
+from .ssm import (TRACE_PARTS, SsmSmooth, SsmTrace, backward_buffers, backward_by_name, batch_arguments, smooth_buffers,
+                  smooth_by_name, smooth_parts, trace_buffers, trace_by_name, trace_parts)
 
 _D = C.POINTER(C.c_double)
 _I32P = C.POINTER(C.c_int32)
@@ -43,6 +43,7 @@ class SsmBatchResult:
     log_evidence = n_resamples = last_resampled = ess = cols = log_weights = last_ancestors = None
     mean = var = log_evidence_trace = None
     paths = smean = svar = None
+    backward = None   # with backward=M: a list of B SsmBackward
 
 
 class Context:
@@ -478,7 +479,8 @@ class Context:
         check(self._L.wsmc_debug_lgssm(self._h, int(steps), None))
 
     def ssm_run(self, spec, data, ess_perc_min=1.0, scheme: int = abi.RESAMPLE_STRATIFIED,
-                want_evidence: bool = True, ess_trace: bool = False, T: int | None = None, trace=False, smooth=False):
+                want_evidence: bool = True, ess_trace: bool = False, T: int | None = None, trace=False, smooth=False,
+                backward: int = 0, backward_seed: int = 0, record: bool = False):
         """A scalar state-space model (wsmc.SSM) as one call (wsmc_ssm_run): the same columns,
         weights, ancestors, state, tape and RNG positions as spec.statements(self, data, ...).
         data: T values, or T rows of the spec's data columns (a spec that reads no data takes T).
@@ -493,10 +495,31 @@ class Context:
         (evidence, SsmTrace, SsmSmooth): the final particles' trajectories and the smoothed moments,
         bit for bit those of spec.statements(self, data, smooth=True). smooth may name the parts
         wanted: a subset of ("paths", "mean", "var"). A smoothed run has the persistent route only:
-        what would send ssm_run through the statements raises WSMCError(WSMC_EARG) here."""
+        what would send ssm_run through the statements raises WSMCError(WSMC_EARG) here.
+        backward=M (wsmc_ssm_run_backward) returns (evidence, SsmBackward), with trace as well
+        (evidence, SsmTrace, SsmBackward): M trajectories drawn by forward filtering, backward
+        simulation from backward_seed, bit for bit spec.backward_definition over the record of
+        spec.statements(self, data, record=True); record=True keeps that record in
+        SsmBackward.record. Everything the run leaves on the context is ssm_run(trace=True)'s. The
+        persistent route only, and not together with smooth (two calls)."""
         tab = spec.table(data, T)
         ev = C.c_double()
         sparts = smooth_parts(smooth)
+        if backward:
+            if int(backward) < 0:
+                raise ValueError("backward: the number of trajectories")
+            if sparts or ess_trace:
+                raise ValueError("backward and smooth / ess_trace: make two calls (the ESS% is in trace=(\"ess\",))")
+            steps, S = len(tab), len(spec.cols)
+            buf, out = trace_buffers(trace_parts(trace), (steps,), S)
+            bbuf, bo = backward_buffers(steps, S, self.n, int(backward), record=record)
+            check(self._L.wsmc_ssm_run_backward(self._h, C.byref(spec.spec), _dptr(tab) if tab.size else None, steps,
+                                                float(ess_perc_min), int(scheme), C.byref(ev) if want_evidence else None,
+                                                C.byref(out), int(backward), int(backward_seed) & (2**64 - 1), C.byref(bo)))
+            tr = (SsmTrace(*trace_by_name(buf, spec.cols)),) if trace else ()
+            return ((float(ev.value) if want_evidence else None),) + tr + (backward_by_name(bbuf, spec.cols),)
+        if record:
+            raise ValueError("record=True needs backward=M (the record is the backward pass's)")
         if sparts and ess_trace:
             raise ValueError("ess_trace and smooth: ask for the ESS% with trace=(\"ess\",)")
         if trace or sparts:
@@ -522,6 +545,34 @@ class Context:
         e = float(ev.value) if want_evidence else None
         return (e, tr) if ess_trace else e
 
+    def ssm_backward(self, spec, data, record, M: int, seed: int, T: int | None = None):
+        """Forward filtering, backward simulation over a record the caller holds (wsmc_ssm_backward):
+        M trajectories as an SsmBackward, bit for bit spec.backward_definition(make_backend, record,
+        data, M, seed). record: an SsmRecord (spec.statements(..., record=True), or
+        ssm_run(backward=M, record=True)'s). This context gives the device and the stream; its
+        particles and state are not touched."""
+        tab = spec.table(data, T)
+        steps, S = len(tab), len(spec.cols)
+        if record.cols.shape[:2] != (steps, S):
+            raise ValueError(f"record: {record.cols.shape[0]} steps of {record.cols.shape[1]} columns, the call has {steps} of {S}")
+        n = record.cols.shape[2]
+        bbuf, bo = backward_buffers(steps, S, n, int(M))
+        check(self._L.wsmc_ssm_backward(self._h, C.byref(spec.spec), _dptr(tab) if tab.size else None, steps, _dptr(record.cols),
+                                        _dptr(record.log_weights), n, int(M), int(seed) & (2**64 - 1), C.byref(bo)))
+        bw = backward_by_name(bbuf, spec.cols)
+        bw.record = record
+        return bw
+
+    def ssm_backward_stats(self) -> dict:
+        """wsmc_debug_ssm_backward's figures of the last backward pass on this context: device seconds
+        of the run's segments (0 for ssm_backward), of the backward kernel and of the rows kernel, the
+        bytes of the record and the outputs, and the segments this context has launched on the
+        backward-recording kernels (cumulative; no other run launches them)."""
+        st = (C.c_int64 * 5)()
+        check(self._L.wsmc_debug_ssm_backward(self._h, st))
+        return {"segments_s": st[0] / 1e6, "backward_s": st[1] / 1e6, "rows_s": st[2] / 1e6, "bytes": int(st[3]),
+                "recording_segments": int(st[4])}
+
     def ssm_stats(self) -> dict:
         """wsmc_debug_ssm's counters: the persistent kernel's particle cap for 1..4 columns, the runs
         it took, the runs that went through the statement route, the segments launched
@@ -539,7 +590,8 @@ class Context:
 
     def ssm_run_batch(self, specs, data, n: int, seeds, ess_perc_min=1.0, scheme: int = abi.RESAMPLE_STRATIFIED,
                       ess_trace: bool = False, state: bool = False, T: int | None = None,
-                      trace: bool = False, smooth=False) -> "SsmBatchResult":
+                      trace: bool = False, smooth=False, backward: int = 0, backward_seeds=None,
+                      record: bool = False) -> "SsmBatchResult":
         """B = len(seeds) independent filters of n particles in one call (wsmc_ssm_run_batch), one
         persistent workgroup each: filter b is, bit for bit, ssm_run(spec b, table b) on a fresh
         Context(n, seed=seeds[b]). This context gives the device and the stream; its own particles
@@ -553,8 +605,18 @@ class Context:
         `log_evidence_trace` [B, T]: row b is ssm_run(trace=True)'s SsmTrace of filter b.
         smooth=True, or a subset of ("paths", "mean", "var") (wsmc_ssm_run_batch_smoothed), fills
         `paths` (name -> [B, T, n]), `smean` and `svar` (name -> [B, T]): row b is
-        ssm_run(smooth=True)'s SsmSmooth of filter b (its log_weights are `log_weights` with state)."""
+        ssm_run(smooth=True)'s SsmSmooth of filter b (its log_weights are `log_weights` with state).
+        backward=M with backward_seeds [B] (wsmc_ssm_run_batch_backward; not with smooth) fills
+        `backward`, a list of B SsmBackward: filter b's is ssm_run(backward=M,
+        backward_seed=backward_seeds[b])'s on a fresh Context(n, seed=seeds[b]), with its record
+        when record=True."""
         sparts = smooth_parts(smooth)
+        if backward and sparts:
+            raise ValueError("backward and smooth: make two calls")
+        if backward and (int(backward) < 0 or backward_seeds is None or len(backward_seeds) != len(seeds)):
+            raise ValueError("backward: the number of trajectories, and one backward seed per filter")
+        if record and not backward:
+            raise ValueError("record=True needs backward=M (the record is the backward pass's)")
         spec_list, tabs, seeds_a = batch_arguments(specs, data, n, seeds, T)   # (before any device call)
         B, first, steps = len(seeds_a), spec_list[0], len(tabs[0])
         tab = np.ascontiguousarray(np.stack(tabs)) if tabs[0].size else None
@@ -583,7 +645,13 @@ class Context:
             out.last_ancestors = res.last_ancestors.ctypes.data_as(_I32P)
         args = (self._h, arr, len(spec_list), _dptr(tab) if tab is not None else None, len(tabs), steps, int(n), B,
                 seeds_a.ctypes.data_as(C.POINTER(C.c_uint64)), float(ess_perc_min), int(scheme), C.byref(out))
-        if sparts:
+        if backward:
+            bbuf, bo = backward_buffers(steps, S, int(n), int(backward), lead=(B,), record=record)
+            bseeds = np.ascontiguousarray(np.asarray([int(s) & (2**64 - 1) for s in backward_seeds], dtype=np.uint64))
+            check(self._L.wsmc_ssm_run_batch_backward(*args, C.byref(tr), int(backward), bseeds.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                      C.byref(bo)))
+            res.backward = [backward_by_name({k: v[b] for k, v in bbuf.items()}, first.cols) for b in range(B)]
+        elif sparts:
             sbuf, so = smooth_buffers(sparts, (B, steps), S, int(n))
             check(self._L.wsmc_ssm_run_batch_smoothed(*args, C.byref(tr), C.byref(so)))
             res.paths, res.smean, res.svar = smooth_by_name(sbuf, first.cols)

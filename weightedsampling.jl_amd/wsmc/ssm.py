@@ -191,6 +191,110 @@ class SsmSmooth:
         return {name: p[:, idx].T.copy() for name, p in self.paths.items()}
 
 
+class SsmRecord:
+    """What a filter leaves for backward simulation: `cols` [T, S, n], every column at each trace
+    point (after step t's last observe, before the Resample that follows it), in the spec's order,
+    and `log_weights` [T, n], the log-weights there."""
+
+    def __init__(self, cols, log_weights):
+        self.cols = np.ascontiguousarray(np.asarray(cols, dtype=np.float64))
+        self.log_weights = np.ascontiguousarray(np.asarray(log_weights, dtype=np.float64))
+        if self.cols.ndim != 3 or self.log_weights.shape != (self.cols.shape[0], self.cols.shape[2]):
+            raise ValueError("record: cols [T, S, n] and log_weights [T, n]")
+
+
+class SsmBackward:
+    """M trajectories drawn by forward filtering, backward simulation (include/wsmc.h
+    wsmc_ssm_backward): `idx` [T, M] int32, the filter particle trajectory m passes through at
+    trace point t; `paths` (column name -> [T, M]) the record's columns there; `mean` / `var`
+    (name -> [T]) E[x_t | y_1:T] and the uncorrected variance over the M equal-weight
+    trajectories (Context.weighted_moments of row t on M particles with fresh weights); `record`
+    the SsmRecord they were drawn from, when asked for. An auxiliary column assigned from the old
+    state (kitagawa's m, the guided spec's xp and m) holds in row t+1 the filter particle's own
+    value: f of its genealogical parent, not f of the drawn x_t."""
+
+    def __init__(self, idx, paths, mean, var, record=None):
+        self.idx, self.paths, self.mean, self.var, self.record = idx, paths, mean, var, record
+
+    def draw(self, k: int) -> dict:
+        """the first k trajectories (name -> [k, T]): they are already equal-weight draws"""
+        k = int(k)
+        if not 0 <= k <= self.idx.shape[1]:
+            raise ValueError(f"draw: {k} of {self.idx.shape[1]} trajectories")
+        return {name: p[:, :k].T.copy() for name, p in self.paths.items()}
+
+
+def backward_buffers(T: int, S: int, n: int, M: int, lead: tuple = (), record: bool = False):
+    """(arrays by part, SsmBackwardOut pointing at them) of a backward pass, as trace_buffers"""
+    buf = {"idx": np.empty(lead + (T, M), dtype=np.int32), "paths": np.empty(lead + (T, S, M)),
+           "mean": np.empty(lead + (T, S)), "var": np.empty(lead + (T, S))}
+    if record:
+        buf["particles"] = np.empty(lead + (T, S, n))
+        buf["log_weights"] = np.empty(lead + (T, n))
+    out = abi.SsmBackwardOut()
+    for p, a in buf.items():
+        setattr(out, p, a.ctypes.data_as(C.POINTER(C.c_int32 if p == "idx" else C.c_double)))
+    return buf, out
+
+
+def backward_by_name(buf: dict, cols) -> SsmBackward:
+    """backward_buffers' arrays of one filter as an SsmBackward"""
+    rec = SsmRecord(buf["particles"], buf["log_weights"]) if "particles" in buf else None
+    return SsmBackward(buf["idx"], {c: buf["paths"][:, k, :] for k, c in enumerate(cols)},
+                       _by_name(buf["mean"], cols), _by_name(buf["var"], cols), rec)
+
+
+def _operand_reads(o) -> int:
+    """the spec columns an operand reads, as a bit mask (a data slot is no column)"""
+    return (1 << o.col[0] if o.col[0] >= 0 else 0) | (1 << o.col[1] if o.col[1] >= 0 else 0)
+
+
+def _dist_reads(d) -> int:
+    return _operand_reads(d.mu[0]) | _operand_reads(d.scale)
+
+
+def _fold_operand(o, ids, patch):
+    """the operand over column ids, its data slot removed: the step's value goes to c0 through
+    `patch`, a list of (object, field, data column)"""
+    r = Operand()
+    C.memmove(C.byref(r), C.byref(o), C.sizeof(Operand))
+    for k in range(2):
+        if o.col[k] == abi.OPERAND_DATA:
+            patch.append((r, "c0", int(o.comp[k])))
+            r.col[k], r.comp[k], r.coef[k] = -1, 0, 0.0
+        elif o.col[k] >= 0:
+            r.col[k] = ids[o.col[k]]
+    return r
+
+
+def _fold_dist(d, ids, patch):
+    r = abi.Dist()
+    C.memmove(C.byref(r), C.byref(d), C.sizeof(abi.Dist))
+    for k in range(4):
+        ops = []
+        r.mu[k] = _fold_operand(d.mu[k], ids, ops)
+        patch += [(r.mu[k], f, j) for _, f, j in ops]   # (a view into r: the copy above is not)
+    ops = []
+    r.scale = _fold_operand(d.scale, ids, ops)
+    patch += [(r.scale, f, j) for _, f, j in ops]
+    return r
+
+
+def _fold_prog(s, ids, patch):
+    """(program, lengths) of an ASSIGN_EXPR over column ids, a data read turned into a constant"""
+    prog = (abi.XInst * s.prog_len)()
+    for k in range(s.prog_len):
+        prog[k] = s.prog[k]
+        if prog[k].op != abi.X_COL:
+            continue
+        if prog[k].col == abi.OPERAND_DATA:
+            patch.append((prog[k], "c", int(prog[k].comp)))
+            prog[k].op, prog[k].col, prog[k].comp = abi.X_CONST, -1, 0
+        else:
+            prog[k].col = ids[prog[k].col]
+    return prog, [int(s.prog_len)]
+
+
 STORE_COLUMNS = 4096   # the columns one context's store holds
 
 
@@ -324,7 +428,8 @@ class SSM:
 
     # ---- the executable definition ----
     def statements(self, backend, data, ess_perc_min: float = 1.0, scheme: int = abi.RESAMPLE_STRATIFIED,
-                   wait: bool = True, T: int | None = None, trace: bool = False, smooth: bool = False):
+                   wait: bool = True, T: int | None = None, trace: bool = False, smooth: bool = False,
+                   record: bool = False):
         """Issue the spec's statements one by one on `backend` (a Context or the tests' Oracle: any
         object with the operator methods), each `sample` / `observe` followed by its Resample, the
         step's data folded into constants: a data slot of an operand is removed and its value
@@ -337,7 +442,11 @@ class SSM:
         column's values at each trace point in a column of their own, `name@t` (an exact copy, a -0.0
         included), which the Resamples that follow gather like any other, and reads them after the
         last step: the result gains an SsmSmooth as its last member, the definition of what
-        Context.ssm_run(smooth=True) returns."""
+        Context.ssm_run(smooth=True) returns. record=True (with wait) also downloads every column and
+        the log-weights at each trace point: the result gains an SsmRecord as its last member, what
+        backward_definition draws from and what Context.ssm_run(backward=M) logs on the device."""
+        if record and not wait:
+            raise ValueError("record=True needs wait=True (the trace point is a synchronisation)")
         if trace and not wait:
             raise ValueError("trace=True needs wait=True (the trace point is a synchronisation)")
         if smooth and not wait:
@@ -353,27 +462,10 @@ class SSM:
         # every statement is built once (ids mapped, data slots removed); a step only writes its
         # data values into the slots listed in `patch`: (object, field, data column)
         def fold_operand(o, patch):
-            r = Operand()
-            C.memmove(C.byref(r), C.byref(o), C.sizeof(Operand))
-            for k in range(2):
-                if o.col[k] == abi.OPERAND_DATA:
-                    patch.append((r, "c0", int(o.comp[k])))
-                    r.col[k], r.comp[k], r.coef[k] = -1, 0, 0.0
-                elif o.col[k] >= 0:
-                    r.col[k] = ids[o.col[k]]
-            return r
+            return _fold_operand(o, ids, patch)
 
         def fold_dist(d, patch):
-            r = abi.Dist()
-            C.memmove(C.byref(r), C.byref(d), C.sizeof(abi.Dist))
-            for k in range(4):
-                ops = []
-                r.mu[k] = fold_operand(d.mu[k], ops)
-                patch += [(r.mu[k], f, j) for _, f, j in ops]   # (a view into r: the copy above is not)
-            ops = []
-            r.scale = fold_operand(d.scale, ops)
-            patch += [(r.scale, f, j) for _, f, j in ops]
-            return r
+            return _fold_dist(d, ids, patch)
 
         def prepare(s):
             """(call, patch): call(waited) issues the statement and its Resample"""
@@ -405,17 +497,7 @@ class SSM:
                 def call(waited):
                     backend.assign(out, e)
             elif s.kind == abi.SSM_ASSIGN_EXPR:
-                prog = (abi.XInst * s.prog_len)()
-                lens = [int(s.prog_len)]
-                for k in range(s.prog_len):
-                    prog[k] = s.prog[k]
-                    if prog[k].op != abi.X_COL:
-                        continue
-                    if prog[k].col == abi.OPERAND_DATA:
-                        patch.append((prog[k], "c", int(prog[k].comp)))
-                        prog[k].op, prog[k].col, prog[k].comp = abi.X_CONST, -1, 0
-                    else:
-                        prog[k].col = ids[prog[k].col]
+                prog, lens = _fold_prog(s, ids, patch)
 
                 def call(waited):
                     backend.assign_expr(out, prog, lens)
@@ -441,6 +523,7 @@ class SSM:
             exprs = [Operand.column(ids[k]) for k in range(S)]
 
         hist = []   # smooth: step t's history columns, in the spec's order
+        rec_cols, rec_lw = [], []   # record: the columns and the log-weights at each trace point
 
         def point(t):
             if trace:
@@ -454,13 +537,16 @@ class SSM:
                     copy[0].op, copy[0].col, copy[0].comp = abi.X_COL, i, 0
                     backend.assign_expr(h, copy, [1])
                 hist.append(hs)
+            if record:
+                rec_cols.append(np.stack([backend.col_download(i) for i in ids]))
+                rec_lw.append(backend.weights_download())
 
         for t in range(T):
             row = tab[t]
             for q, (call, patch) in enumerate(step):
                 for obj, field, j in patch:
                     setattr(obj, field, row[j])
-                if (trace or smooth) and q == last:
+                if (trace or smooth or record) and q == last:
                     r = call(True, lambda: point(t))
                 else:
                     r = call(wait and q == last)
@@ -482,4 +568,164 @@ class SSM:
             sm = SsmSmooth(paths, {c: smean[:, k].copy() for k, c in enumerate(self.cols)},
                            {c: svar[:, k].copy() for k, c in enumerate(self.cols)}, backend.weights_download())
             out = out + (sm,)
+        if record:
+            out = out + (SsmRecord(np.stack(rec_cols), np.stack(rec_lw)),)
         return out
+
+    # ---- backward simulation ----
+    def backward_terms(self) -> list:
+        """The step statements whose log-density enters the backward weight of forward filtering,
+        backward simulation, as indices into `step`: wsmc_ssm_spec_backward's rule, restated here.
+        Every column starts tainted (it holds the previous trace point's value); a SAMPLE's term is
+        included iff its dist reads a tainted column, an importance SAMPLE's target's iff it does
+        once the column holds the successor's value, an OBSERVE's or WEIGHT's iff its dist or value
+        does; an assignment is tainted iff its right-hand side is. Raises ValueError with the
+        library's reason for a spec backward simulation is not defined for."""
+        self.check()
+        sp = self.spec
+        S, n = sp.n_cols, sp.n_step
+        name = lambda k: self.cols[k]
+        if sp.step[n - 1].kind != abi.SSM_OBSERVE:
+            raise ValueError("ssm backward: the step's last statement is not its last OBSERVE (the trace point)")
+        drawn = [0] * S
+        writes = [0] * S
+        for q in range(n):
+            s = sp.step[q]
+            if s.kind in (abi.SSM_OBSERVE, abi.SSM_WEIGHT):
+                continue
+            writes[s.col] += 1
+            drawn[s.col] += s.kind in (abi.SSM_SAMPLE, abi.SSM_SAMPLE_IMPORTANCE)
+        for k in range(S):
+            if drawn[k] and writes[k] > 1:
+                raise ValueError(f"ssm backward: column {name(k)} is written by a SAMPLE and by another statement of the step")
+        tainted, written, state, included = (1 << S) - 1, 0, 0, []
+        for q in range(n):
+            s = sp.step[q]
+            if s.kind == abi.SSM_SAMPLE:
+                r = _dist_reads(s.dist)
+                state |= r & ~written
+                if r & tainted:
+                    included.append(q)
+                tainted &= ~(1 << s.col)
+                written |= 1 << s.col
+            elif s.kind == abi.SSM_SAMPLE_IMPORTANCE:
+                state |= _dist_reads(s.dist) & ~written   # the draw reads the proposal before the store
+                tainted &= ~(1 << s.col)
+                written |= 1 << s.col
+                r = _dist_reads(s.target)
+                state |= r & ~written
+                if r & tainted:
+                    included.append(q)
+            elif s.kind in (abi.SSM_ASSIGN, abi.SSM_ASSIGN_EXPR):
+                if s.kind == abi.SSM_ASSIGN:
+                    r = _operand_reads(s.value)
+                else:
+                    r = 0
+                    for k in range(s.prog_len):
+                        if s.prog[k].op == abi.X_COL and s.prog[k].col >= 0:
+                            r |= 1 << s.prog[k].col
+                state |= r & ~written
+                tainted = tainted | (1 << s.col) if r & tainted else tainted & ~(1 << s.col)
+                written |= 1 << s.col
+            else:
+                r = _dist_reads(s.dist) | _operand_reads(s.value)
+                state |= r & ~written
+                if r & tainted:
+                    included.append(q)
+        for k in range(S):
+            if state & tainted & (1 << k):
+                raise ValueError(f"ssm backward: state column {name(k)} still holds the previous step's value at the end of the "
+                                 "step (a static parameter or a deterministic carry-over: the transition is a Dirac)")
+        return included
+
+    def backward_definition(self, make_backend, record, data, M: int, seed: int, T: int | None = None) -> SsmBackward:
+        """Forward filtering, backward simulation, operator by operator: the definition of what
+        Context.ssm_backward and Context.ssm_run(backward=M) return. make_backend(n, seed) gives a
+        fresh context (a Context or the tests' Oracle); record is the filter's SsmRecord.
+        Trajectory m = 0 .. M-1, going t = T-1 down to 0 on a scratch backend of n particles and
+        seed `seed`: the weights are log_weights[t]; for t < T-1 the columns are cols[t] and step
+        t+1's statements are issued in order with data row t+1 folded in and z = cols[t+1][:,
+        idx[t+1][m]] the successor's row: a SAMPLE as weight(dist, z[col]) if included, then
+        assign(col, z[col]); an importance SAMPLE as assign(col, z[col]), then weight(target, col) if
+        included; an assignment as it is; an OBSERVE or WEIGHT as weight(dist, value) if included;
+        no Resample. Then set_op_counter(t M + m) and sample_particles(1) give idx[t][m]. paths
+        gathers the record through idx; mean / var are weighted_moments of each row on an
+        M-particle backend with fresh weights. A draw that fails (exp_norm of the weights is NaN)
+        raises WSMCError(WSMC_ESTATE)."""
+        included = set(self.backward_terms())
+        sp = self.spec
+        tab = self.table(data, T)
+        T, M, S = len(tab), int(M), len(self.cols)
+        cols, lw = record.cols, record.log_weights
+        if M < 1:
+            raise ValueError("M: at least one trajectory")
+        if cols.shape[:2] != (T, S):
+            raise ValueError(f"record: {cols.shape[0]} steps of {cols.shape[1]} columns, the call has {T} of {S}")
+        n = cols.shape[2]
+        idx = np.empty((T, M), dtype=np.int32)
+        for m in range(M):
+            be = make_backend(n, seed)
+            ids = [be.col_create(name, 1) for name in self.cols]
+            stmts = []   # (kind, included, out column, the folded parts, patch)
+            for q in range(sp.n_step):
+                s, patch = sp.step[q], []
+                if s.kind == abi.SSM_SAMPLE:
+                    parts = (_fold_dist(s.dist, ids, patch),)
+                elif s.kind == abi.SSM_SAMPLE_IMPORTANCE:
+                    parts = (_fold_dist(s.target, ids, patch),)
+                elif s.kind == abi.SSM_ASSIGN:
+                    parts = ([_fold_operand(s.value, ids, patch)],)
+                elif s.kind == abi.SSM_ASSIGN_EXPR:
+                    parts = _fold_prog(s, ids, patch)
+                else:
+                    parts = (_fold_dist(s.dist, ids, patch), [_fold_operand(s.value, ids, patch)])
+                out = ids[s.col] if s.kind not in (abi.SSM_OBSERVE, abi.SSM_WEIGHT) else -1
+                stmts.append((s.kind, q in included, int(s.col), out, parts, patch))
+            for t in range(T - 1, -1, -1):
+                be.weights_upload(lw[t])
+                if t < T - 1:
+                    for k in range(S):
+                        be.col_upload(ids[k], cols[t][k])
+                    z, row = cols[t + 1][:, idx[t + 1][m]], tab[t + 1]
+                    for kind, inc, col, out, parts, patch in stmts:
+                        for obj, field, j in patch:
+                            setattr(obj, field, row[j])
+                        if kind == abi.SSM_SAMPLE:
+                            if inc:
+                                be.weight(parts[0], [Operand.const(z[col])])
+                            be.assign(out, [Operand.const(z[col])])
+                        elif kind == abi.SSM_SAMPLE_IMPORTANCE:
+                            be.assign(out, [Operand.const(z[col])])
+                            if inc:
+                                be.weight(parts[0], [Operand.column(out)])
+                        elif kind == abi.SSM_ASSIGN:
+                            be.assign(out, parts[0])
+                        elif kind == abi.SSM_ASSIGN_EXPR:
+                            be.assign_expr(out, parts[0], parts[1])
+                        elif inc:
+                            be.weight(parts[0], parts[1])
+                be.set_op_counter(t * M + m)
+                try:
+                    idx[t][m] = be.sample_particles(1, True)[0]
+                except RuntimeError as e:   # a Context's WSMCError, or the oracle's own error with the code
+                    code = e.code if isinstance(e, abi.WSMCError) else abi.WSMC_ESTATE if f"({abi.WSMC_ESTATE})" in str(e) else None
+                    if code != abi.WSMC_ESTATE:
+                        raise
+                    raise abi.WSMCError(abi.WSMC_ESTATE, f"ssm backward: exp_norm of the weights is NaN at step {t} "
+                                                         f"of trajectory {m}") from None
+            if hasattr(be, "close"):
+                be.close()
+        paths = np.stack([cols[t][:, idx[t]] for t in range(T)])   # [T, S, M]
+        mean, var = np.empty((T, S)), np.empty((T, S))
+        be = make_backend(M, seed)
+        ids = [be.col_create(name, 1) for name in self.cols]
+        exprs = [Operand.column(i) for i in ids]
+        for t in range(T):
+            for k in range(S):
+                be.col_upload(ids[k], paths[t][k])
+            mu, cv = be.weighted_moments(exprs)
+            mean[t], var[t] = mu, np.diagonal(cv)
+        if hasattr(be, "close"):
+            be.close()
+        return SsmBackward(idx, {c: paths[:, k, :] for k, c in enumerate(self.cols)}, _by_name(mean, self.cols),
+                           _by_name(var, self.cols), record)
