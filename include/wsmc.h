@@ -749,6 +749,54 @@ int wsmc_ssm_run_batch_backward(wsmc_ctx* ctx, const wsmc_ssm_spec* specs, int32
  * segments launched on the backward-recording kernels, cumulative per context (no other entry
  * point launches them). */
 int wsmc_debug_ssm_backward(wsmc_ctx* ctx, int64_t* stats_out);
+/* ---- conditional SMC: a filter run conditionally on a trajectory (particle Gibbs) ----------------
+ * A conditional run of `spec` over `data` with a reference trajectory ref[T][n_cols] is the
+ * unconditional run with two changes; particle n-1 is the reference particle.
+ *   Pin. In `step`, never in `init`, right after a SAMPLE col ~ dist of step t has stored its
+ *   draws, row n-1 of col becomes ref[t][col] (wsmc_sample, then wsmc_col_download, the last entry
+ *   set, wsmc_col_upload). Every other particle keeps its draw; assignments recompute their columns
+ *   for row n-1 from the pinned values; entries of ref for columns no SAMPLE of the step writes are
+ *   ignored. `init` is not pinned (the record has no row for it): the run is conditional SMC for
+ *   the model with `init` integrated out.
+ *   Conditional Resample. The decision, the ESS, the evidence and the reset of the weights to the
+ *   log-mean are the ordinary Resample's. When it runs, the ancestors are n independent draws with
+ *   slot n-1 forced: idx[j] is wsmc_sample_particles(n, replace)'s draw j on the weights the
+ *   Resample met, keyed by the op counter r the Resample takes (the first index whose running sum
+ *   of the wsmc_qweight integers exceeds wsmc_multi_target(wsmc_multi_word(seed, r, j), Q)), then
+ *   idx[n-1] = n-1. In operators: read the op counter r, the weights and every column; wsmc_resample
+ *   (stratified); if it ran (wsmc_get_state's n_resamples grew: a Resample that meets unchanged
+ *   weights, as after a SAMPLE, does nothing), wsmc_weights_upload of the saved weights to a scratch context of the
+ *   same n and seed, wsmc_set_op_counter(r) and wsmc_sample_particles(n, 1) there, the last index
+ *   forced, wsmc_col_upload(k, saved[k][idx]) for every column. Forcing a slot is exact for
+ *   independent draws only, so there is no scheme argument.
+ * Which columns are pinned, and which specs are eligible (host only, no context): pinned[k] is set
+ * to 1 for a column a SAMPLE of `step` writes, else 0. WSMC_EARG, with the reason in
+ * wsmc_last_error(): a spec wsmc_ssm_spec_check refuses; one that holds an importance SAMPLE or a
+ * WEIGHT (pinning an importance Sample needs its weight term at the pinned value); an `init` that
+ * holds anything but SAMPLE and assignments; a spec wsmc_ssm_spec_backward refuses (every state
+ * column is then redrawn each step, so the pinned rows determine the reference particle). */
+int wsmc_ssm_spec_conditional(const wsmc_ssm_spec* spec, int32_t pinned[WSMC_SSM_MAX_COLS]);
+/* B conditional runs in one call, one persistent workgroup each: filter b is, bit for bit, the
+ * definition above on a fresh wsmc_create(n, seeds[b]) context with reference[b] ([B][T][n_cols],
+ * the spec's column order), and out, trace and the record are what wsmc_ssm_run_batch_backward
+ * gives for it (out->last_ancestors: idx of the last Resample that ran). The record is always
+ * logged. With M >= 1 filter b's backward pass is wsmc_ssm_backward's over its record with
+ * bw_seeds[b]: a conditional sweep followed by one backward trajectory is the particle Gibbs
+ * kernel with backward sampling, which leaves p(x_0:T-1 | y) invariant. M = 0 runs no backward
+ * kernel: bw_seeds may be NULL, and bw_out may be NULL or ask for particles / log_weights alone.
+ * ctx gives the device and the stream only (as in wsmc_ssm_run_batch). WSMC_EARG:
+ * wsmc_ssm_run_batch_backward's refusals, wsmc_ssm_spec_conditional's for every spec ("spec b:
+ * ..."), a null reference, M < 0. WSMC_ENOMEM and WSMC_ESTATE as there. */
+int wsmc_ssm_run_conditional(wsmc_ctx* ctx, const wsmc_ssm_spec* specs, int32_t n_specs,
+                             const double* data, int32_t n_tables, int32_t T, int32_t n, int32_t B,
+                             const uint64_t* seeds, double ess_perc_min, const double* reference,
+                             wsmc_ssm_batch_out* out, const wsmc_ssm_trace* trace, int32_t M,
+                             const uint64_t* bw_seeds, const wsmc_ssm_backward_out* bw_out);
+/* stats_out[5] = the last conditional batch on ctx: device time (HIP events on the stream) of its
+ * segments, of the backward kernel and of the rows and moments kernel, microseconds, and the bytes
+ * the call allocated for the record, the references and the outputs; then the segments launched on
+ * the conditional kernels, cumulative per context (no other entry point launches them). */
+int wsmc_debug_ssm_conditional(wsmc_ctx* ctx, int64_t* stats_out);
 /* per-kernel timing of the last fused run (HIP events on the ctx stream), ms */
 typedef struct {
     double total_ms;            /* whole run, first kernel to last                       */

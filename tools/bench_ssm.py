@@ -57,7 +57,17 @@ persistent run untraced, the run with M backward-simulated trajectories (the who
 smoothed run with paths for context, and on the same box a vectorised numpy FFBS of the same
 sizes over the run's own record (the baseline: float64 numpy, its own random stream, not
 bit-compared). The backward kernel's and the rows kernel's device times are the library's own (HIP
-events, Context.ssm_backward_stats). Lines go to profiles/ssm_backward.jsonl."""
+events, Context.ssm_backward_stats). Lines go to profiles/ssm_backward.jsonl.
+
+    python tools/bench_ssm.py --conditional              lgssm and sv at T = 1e3, B = 1 and 256
+    python tools/bench_ssm.py --conditional --leg sv --T 1000 --B 256
+
+The conditional leg (wsmc_ssm_run_conditional), forced resampling, N = 1e3: one particle-Gibbs
+sweep, the conditional batch with one backward trajectory a filter, beside ssm_run_batch(backward=1)
+of the same shape (the yardstick: the same kernels but for the pin and the Resample's ancestors),
+alternated over rounds on one context; at B = 1 also the same sweep through
+SSM.conditional_definition and SSM.backward_definition on Contexts (the operators, with their
+downloads and uploads at every Resample), once. Lines go to profiles/ssm_conditional.jsonl."""
 import argparse
 import json
 import pathlib
@@ -75,6 +85,7 @@ OUT_TRACE = ROOT / "profiles" / "ssm_trace.jsonl"
 OUT_SMOOTH = ROOT / "profiles" / "ssm_smooth.jsonl"
 OUT_GUIDED = ROOT / "profiles" / "ssm_guided.jsonl"
 OUT_BACKWARD = ROOT / "profiles" / "ssm_backward.jsonl"
+OUT_CONDITIONAL = ROOT / "profiles" / "ssm_conditional.jsonl"
 
 
 def best_of(run, reps=2):
@@ -452,6 +463,81 @@ def child_backward(leg: str, T: int, M: int) -> dict:
     return out
 
 
+def child_conditional(leg: str, T: int, B: int) -> dict:
+    import statistics
+    import numpy as np
+    import wsmc
+    from wsmc import models
+    spec, data = (models.lgssm1d_spec(), models.lgssm1d_data(T)) if leg == "lgssm" else (models.sv(), models.sv_data(T))
+    spec.check()
+    seeds, bw_seeds = wsmc.pg_seeds(42, 0, B)
+    ctx = wsmc.Context(16, seed=1)
+    last = {}
+
+    def unconditional():
+        last["unconditional"] = ctx.ssm_run_batch(spec, data, N, seeds, ess_perc_min=1.0, backward=1, backward_seeds=bw_seeds)
+        last["unconditional_stats"] = ctx.ssm_backward_stats()
+
+    unconditional()   # (also the first sweep: its trajectories are the reference)
+    ref = np.stack([np.stack([last["unconditional"].backward[b].paths[c][:, 0] for c in spec.cols], axis=1) for b in range(B)])
+
+    def conditional():
+        last["conditional"] = ctx.ssm_run_conditional(spec, data, N, seeds, ref, ess_perc_min=1.0, backward=1, backward_seeds=bw_seeds)
+        last["conditional_stats"] = ctx.ssm_conditional_stats()
+
+    routes = {"unconditional": unconditional, "conditional": conditional}
+    times = {k: [] for k in routes}
+    for rnd in range(7):   # round 0 warms up, rounds 1..6 are the figures, the two routes alternating
+        for name, run in routes.items():
+            ctx.sync()
+            t0 = time.perf_counter()
+            run()
+            if rnd >= 1:
+                times[name].append(time.perf_counter() - t0)
+    assert (last["conditional"].n_resamples == T).all() and (last["unconditional"].n_resamples == T).all()
+    out = {"leg": leg, "N": N, "T": T, "B": B, "M": 1, "columns": len(spec.cols), "segments": ctx.ssm_batch_stats()["segments"]}
+    for k in routes:
+        out[f"{k}_s"] = statistics.median(times[k])
+        out[f"{k}_s_range"] = [min(times[k]), max(times[k])]
+        st = last[k + "_stats"]
+        out[f"{k}_device_s"] = {"segments": st["segments_s"], "backward": st["backward_s"], "rows": st["rows_s"]}
+    out["conditional_over_unconditional"] = out["conditional_s"] / out["unconditional_s"]
+    out["conditional_over_unconditional_segments"] = (last["conditional_stats"]["segments_s"] /
+                                                      last["unconditional_stats"]["segments_s"])
+    ctx.close()
+    if B == 1:   # the same sweep through the operators, once (its Resamples download and upload every column)
+        def make(n, seed):
+            return wsmc.Context(n, seed=seed)
+        t0 = time.perf_counter()
+        rec, end = spec.conditional_definition(make, data, N, int(seeds[0]), ref[0], 1.0)[-2:]
+        t1 = time.perf_counter()
+        bw = spec.backward_definition(make, rec, data, 1, int(bw_seeds[0]))
+        t2 = time.perf_counter()
+        got = last["conditional"]
+        assert end.log_evidence == got.log_evidence[0] and (bw.idx == got.backward[0].idx).all()
+        out.update(definition_filter_s=t1 - t0, definition_backward_s=t2 - t1,
+                   definition_over_conditional=(t2 - t0) / out["conditional_s"])
+    return out
+
+
+def driver_conditional(Ts, legs, Bs) -> int:
+    OUT_CONDITIONAL.parent.mkdir(exist_ok=True)
+    for leg in legs:
+        for T in Ts:
+            for B in Bs:
+                cmd = ["timeout", "-k", "10", "240", sys.executable, __file__, "--conditional", "--leg", leg, "--T", str(T), "--B", str(B)]
+                r = subprocess.run(cmd, capture_output=True, text=True)
+                if r.returncode != 0:
+                    print(f"{leg} T={T} B={B}: exit {r.returncode}\n{r.stdout}\n{r.stderr}", flush=True)
+                    return 1   # nothing more is started on the device
+                line = r.stdout.strip().splitlines()[-1]
+                json.loads(line)
+                with open(OUT_CONDITIONAL, "a") as f:
+                    f.write(line + "\n")
+                print(line, flush=True)
+    return 0
+
+
 def driver_backward(Ts, legs, Ms) -> int:
     OUT_BACKWARD.parent.mkdir(exist_ok=True)
     for leg in legs:
@@ -506,7 +592,14 @@ if __name__ == "__main__":
     ap.add_argument("--guided", action="store_true", help="the guided leg (profiles/ssm_guided.jsonl)")
     ap.add_argument("--backward", action="store_true", help="the backward leg (profiles/ssm_backward.jsonl)")
     ap.add_argument("--M", type=int, action="append", help="the backward leg's trajectories")
+    ap.add_argument("--conditional", action="store_true", help="the conditional leg (profiles/ssm_conditional.jsonl)")
+    ap.add_argument("--B", type=int, action="append", help="the conditional leg's filters")
     a = ap.parse_args()
+    if a.conditional and a.leg:
+        print(json.dumps(child_conditional(a.leg, (a.T or [1000])[0], (a.B or [1])[0])), flush=True)
+        sys.exit(0)
+    if a.conditional:
+        sys.exit(driver_conditional(a.T or [1000], a.legs.split(",") if a.legs != ",".join(LEGS) else ["lgssm", "sv"], a.B or [1, 256]))
     if a.backward and a.leg:
         print(json.dumps(child_backward(a.leg, (a.T or [1000])[0], (a.M or [64])[0])), flush=True)
         sys.exit(0)

@@ -6055,6 +6055,51 @@ int wsmc_debug_ssm_backward(wsmc_ctx* c, int64_t* stats_out) {
     return WSMC_OK;
 }
 
+// wsmc_ssm_spec_conditional's rule on a checked spec (include/wsmc.h): the pinned columns, or the
+// first reason a conditional run is not defined for the spec
+static std::string ssm_conditional_why(const wsmc_ssm_spec* sp, int32_t* pinned) {
+    for (int k = 0; k < WSMC_SSM_MAX_COLS; ++k) pinned[k] = 0;
+    for (int part = 0; part < 2; ++part) {
+        const wsmc_ssm_stmt* stmts = part ? sp->step : sp->init;
+        const std::string where = part ? "step" : "init";
+        for (int q = 0; q < (part ? sp->n_step : sp->n_init); ++q) {
+            const int kind = stmts[q].kind;
+            if (kind == WSMC_SSM_SAMPLE_IMPORTANCE)
+                return "statement " + std::to_string(q) + " of " + where +
+                       " is an importance SAMPLE (pinning it needs its weight term at the pinned value)";
+            if (kind == WSMC_SSM_WEIGHT)
+                return "statement " + std::to_string(q) + " of " + where + " is a WEIGHT (guided specs are not supported)";
+            if (!part && kind == WSMC_SSM_OBSERVE)
+                return "statement " + std::to_string(q) +
+                       " of init is an OBSERVE (init may hold SAMPLE and assignments only: it is not pinned)";
+        }
+    }
+    int32_t included[WSMC_SSM_MAX_STMTS];
+    const std::string why = ssm_backward_why(sp, included);
+    if (!why.empty()) return "ssm backward: " + why;
+    for (int q = 0; q < sp->n_step; ++q)
+        if (sp->step[q].kind == WSMC_SSM_SAMPLE) pinned[sp->step[q].col] = 1;
+    return std::string();
+}
+
+int wsmc_ssm_spec_conditional(const wsmc_ssm_spec* spec, int32_t* pinned) {
+    if (!pinned) return fail(WSMC_EARG, "null argument");
+    if (int rc = wsmc_ssm_spec_check(spec)) return rc;
+    const std::string why = ssm_conditional_why(spec, pinned);
+    if (!why.empty()) return fail(WSMC_EARG, "ssm conditional: " + why);
+    return WSMC_OK;
+}
+
+int wsmc_debug_ssm_conditional(wsmc_ctx* c, int64_t* stats_out) {
+    if (!c) return fail(WSMC_EARG, "null context");
+    if (c->multi) return fail(WSMC_EARG, "ssm conditional: a multi-device context");
+    if (!stats_out) return fail(WSMC_EARG, "null stats_out");
+    for (int k = 0; k < 3; ++k) stats_out[k] = c->ssm_cond_us[k];
+    stats_out[3] = c->ssm_cond_bytes;
+    stats_out[4] = c->ssm_cond_launches;
+    return WSMC_OK;
+}
+
 // wsmc_ssm_run, wsmc_ssm_run_traced and wsmc_ssm_run_smoothed: tr's and sm's members are null where
 // nothing is wanted
 static int ssm_run(wsmc_ctx* c, const wsmc_ssm_spec* sp, const double* data, int32_t T, double ess_min, int32_t scheme,
@@ -6386,11 +6431,13 @@ int wsmc_ssm_batch_out_sizeof(int64_t* bytes) {
 }
 
 // wsmc_ssm_run_batch, wsmc_ssm_run_batch_traced and wsmc_ssm_run_batch_smoothed: tr's and sm's
-// members are null where nothing is wanted
+// members are null where nothing is wanted. cond_ref: wsmc_ssm_run_conditional's reference
+// trajectories (then bw_out is set, the record is logged, and bw_M may be 0: no backward pass)
 static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_specs, const double* data, int32_t n_tables,
                          int32_t T, int32_t n, int32_t B, const uint64_t* seeds, double ess_min, int32_t scheme,
                          wsmc_ssm_batch_out* out, const wsmc_ssm_trace& tr, const wsmc_ssm_smooth& sm, int32_t bw_M = 0,
-                         const uint64_t* bw_seeds = nullptr, const wsmc_ssm_backward_out* bw_out = nullptr) {
+                         const uint64_t* bw_seeds = nullptr, const wsmc_ssm_backward_out* bw_out = nullptr,
+                         const double* cond_ref = nullptr) {
     // every refusal before any device call; the context's state is never read past its layout
     if (!c) return fail(WSMC_EARG, "null context");
     if (B < 1) return fail(WSMC_EARG, "ssm batch: B < 1");
@@ -6434,6 +6481,7 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
     // one allocation for the call: the state between segments ([B] rows of what a context keeps:
     // zero columns, zero log-weights and a zero ancestors row are what wsmc_create and
     // wsmc_col_create leave), the records, the images, the tables, the trace
+    const bool cond = cond_ref != nullptr;   // (with bw_out)
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t nx = up(sizeof(double) * (size_t)B * S * n), nw = up(sizeof(double) * (size_t)B * n),
                  nanc = up(sizeof(int32_t) * (size_t)B * n), nrec = up(sizeof(SsmBatchRec) * (size_t)B),
@@ -6441,7 +6489,8 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
                  ntarg = sh.guided ? up(sizeof(SsmTarget) * kSsmTargets * (size_t)B) : 0,
                  ntrace = out->ess_trace || tr.ess ? up(sizeof(double) * (size_t)B * T) : 0,
                  nmean = tr.mean ? up(sizeof(double) * (size_t)B * T * S) : 0, nvar = tr.var ? up(sizeof(double) * (size_t)B * T * S) : 0,
-                 nle = tr.log_evidence ? up(sizeof(double) * (size_t)B * T) : 0;
+                 nle = tr.log_evidence ? up(sizeof(double) * (size_t)B * T) : 0,
+                 nref = cond ? up(sizeof(double) * (size_t)B * T * S) : 0;
     const size_t nstate = nx + nw + nanc + nrec;
     const bool smooth = sm.paths || sm.mean || sm.var;
     const size_t nsmooth = smooth ? ssm_smooth_carve(nullptr, sm, B, T, n, sh, nullptr) : 0;
@@ -6450,7 +6499,17 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
     const bool bw = bw_out != nullptr;
     std::vector<SsmBwFilter> bw_filt(bw ? (size_t)B : 0);
     SsmBwReq bw_req;
-    if (bw) {
+    for (int32_t b = 0; cond && b < n_specs; ++b) {
+        int32_t pinned[WSMC_SSM_MAX_COLS];
+        const std::string w = ssm_conditional_why(specs + b, pinned);
+        if (!w.empty()) return fail(WSMC_EARG, "ssm conditional: spec " + std::to_string(b) + ": " + w);
+    }
+    if (cond && bw_M == 0) {
+        if (bw_out->idx || bw_out->paths || bw_out->mean || bw_out->var)
+            return fail(WSMC_EARG, "ssm conditional: M = 0 and a backward output asked for (particles and log_weights alone)");
+        bw_req.M = 0;
+        bw_req.out = *bw_out;
+    } else if (bw) {
         if (!bw_seeds) return fail(WSMC_EARG, "ssm batch backward: null bw_seeds");
         if (bw_M < 1 || bw_M > ssm_cap(S))
             return fail(WSMC_EARG, "ssm batch backward: M = " + std::to_string(bw_M) + " trajectories (1 .. " + std::to_string(ssm_cap(S)) +
@@ -6469,8 +6528,8 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
     SsmSlab slab;
     SsmSmoothClock sm_clock;
     if (bw) {
-        if (int rc = ssm_smooth_alloc(&slab, nstate + nfilt + ndata + ntarg + ntrace + nmean + nvar + nle + nbw + 256, "ssm batch backward",
-                                      "the record and the outputs"))
+        if (int rc = ssm_smooth_alloc(&slab, nstate + nfilt + ndata + ntarg + ntrace + nmean + nvar + nle + nref + nbw + 256,
+                                      cond ? "ssm conditional" : "ssm batch backward", "the record and the outputs"))
             return rc;
         WSMC_HIP(sm_clock.start());
     } else if (smooth) {
@@ -6492,6 +6551,7 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
     double* d_mean = nmean ? reinterpret_cast<double*>(q) : nullptr; q += nmean;
     double* d_var = nvar ? reinterpret_cast<double*>(q) : nullptr; q += nvar;
     double* d_le = nle ? reinterpret_cast<double*>(q) : nullptr; q += nle;
+    double* d_ref = nref ? reinterpret_cast<double*>(q) : nullptr; q += nref;
     SsmSmoothBufs sb;
     std::memset(&sb, 0, sizeof(sb));
     if (smooth) {
@@ -6518,6 +6578,7 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
         if (e == hipSuccess && d_targ)
             e = hipMemcpyAsync(d_targ, targ.data(), sizeof(SsmTarget) * targ.size(), hipMemcpyHostToDevice, st);
         if (e == hipSuccess && bw) e = ssm_bw_stage(st, slab.p, bb, bw_filt.data(), B, nullptr, 0);
+        if (e == hipSuccess && cond) e = hipMemcpyAsync(d_ref, cond_ref, sizeof(double) * (size_t)B * T * S, hipMemcpyHostToDevice, st);
         return e;
     };
     hipError_t e = run();
@@ -6543,7 +6604,7 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
     // steps a launch: the single run's, divided by the rounds of resident workgroups the batch
     // takes, so a launch stays near the single run's 25 ms whatever B is
     int per_cu = 0, cus = 0;
-    if (e == hipSuccess) e = ssm_batch_occupancy(c->device, feat, bw ? (sh.guided ? 6 : 5) : sh.guided ? (smooth ? 4 : 3) : smooth ? 2 : (d_mean || d_var || d_le) ? 1 : 0, threads, ssm_lds_bytes(n, S), &per_cu, &cus);
+    if (e == hipSuccess) e = ssm_batch_occupancy(c->device, feat, cond ? 7 : bw ? (sh.guided ? 6 : 5) : sh.guided ? (smooth ? 4 : 3) : smooth ? 2 : (d_mean || d_var || d_le) ? 1 : 0, threads, ssm_lds_bytes(n, S), &per_cu, &cus);
     if (e == hipSuccess && (per_cu < 1 || cus < 1)) e = hipErrorInvalidValue;
     int64_t nseg = 0;
     if (e == hipSuccess) {
@@ -6555,6 +6616,18 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
         for (int32_t t0 = 0; t0 < T && e == hipSuccess; t0 += K, ++nseg) {
             set_segment(ka, t0, K, T);
             ka.last = t0 + ka.nsteps == T;
+            if (cond) {   // the conditional kernels: the backward-recording arguments and the references
+                SsmBatchCondArgs kc;
+                std::memset(&kc, 0, sizeof(kc));
+                kc.ra.a = ka;
+                kc.ra.r.hist = bb.hist;
+                kc.ra.r.lwlog = bb.lwlog;
+                kc.ra.r.T = T;
+                kc.ref = d_ref;
+                e = launch_ssm_batch_segment_cond(st, kc, feat, threads);
+                c->ssm_cond_launches += 1;
+                continue;
+            }
             if (bw) {   // the recording kernels of a backward batch: the same arguments, the record's log
                 SsmBatchGuidedBwArgs kgb;
                 std::memset(&kgb, 0, sizeof(kgb));
@@ -6575,7 +6648,7 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
     if (e == hipSuccess) e = sm_clock.mark(1, st);
     int32_t bw_flag = 0;
     if (e == hipSuccess && bw) {   // the backward pass over every filter's record: behind the last segment
-        e = ssm_bw_pass(st, bb, sh, B, T, n, bw_req, sm_clock, &bw_flag);
+        if (bw_req.M > 0) e = ssm_bw_pass(st, bb, sh, B, T, n, bw_req, sm_clock, &bw_flag);
         if (e == hipSuccess && bw_out->particles)
             e = hipMemcpyAsync(bw_out->particles, bb.hist, sizeof(double) * (size_t)B * T * S * n, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess && bw_out->log_weights)
@@ -6622,7 +6695,10 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
         if (out->last_resampled) out->last_resampled[b] = r.last_dec;
     }
     if (smooth) sm_clock.read(c, nsmooth);
-    if (bw) {
+    if (cond) {
+        sm_clock.elapsed(c->ssm_cond_us);
+        c->ssm_cond_bytes = (int64_t)(nbw + nref);
+    } else if (bw) {
         sm_clock.elapsed(c->ssm_bw_us);
         c->ssm_bw_bytes = (int64_t)nbw;
     }
@@ -6630,7 +6706,7 @@ static int ssm_run_batch(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_spec
     c->ssm_batch_cus = cus;
     c->ssm_batch_segments = nseg;
     c->ssm_batch_wall_us = us(t_in, clk::now());
-    if (bw_flag) return fail(WSMC_ESTATE, "ssm batch backward: exp_norm of the weights is NaN at some step of some trajectory (the filters themselves are complete)");
+    if (bw_flag) return fail(WSMC_ESTATE, cond ? "ssm conditional: exp_norm of the weights is NaN at some step of some trajectory (the filters themselves are complete)" : "ssm batch backward: exp_norm of the weights is NaN at some step of some trajectory (the filters themselves are complete)");
     return WSMC_OK;
 }
 
@@ -6660,6 +6736,19 @@ int wsmc_ssm_run_batch_backward(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t
     if (!bw_out) return fail(WSMC_EARG, "ssm batch backward: null bw_out");
     return ssm_run_batch(c, specs, n_specs, data, n_tables, T, n, B, seeds, ess_min, scheme, out, trace ? *trace : kNoTrace, kNoSmooth, M,
                          bw_seeds, bw_out);
+}
+
+int wsmc_ssm_run_conditional(wsmc_ctx* c, const wsmc_ssm_spec* specs, int32_t n_specs, const double* data, int32_t n_tables,
+                             int32_t T, int32_t n, int32_t B, const uint64_t* seeds, double ess_min, const double* reference,
+                             wsmc_ssm_batch_out* out, const wsmc_ssm_trace* trace, int32_t M, const uint64_t* bw_seeds,
+                             const wsmc_ssm_backward_out* bw_out) {
+    if (!reference) return fail(WSMC_EARG, "ssm conditional: null reference");
+    if (M < 0) return fail(WSMC_EARG, "ssm conditional: M < 0");
+    if (M > 0 && !bw_out) return fail(WSMC_EARG, "ssm conditional: null bw_out");
+    static const wsmc_ssm_backward_out kNoBackward = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // (the scheme decides nothing in a conditional Resample: the ancestors are independent draws)
+    return ssm_run_batch(c, specs, n_specs, data, n_tables, T, n, B, seeds, ess_min, WSMC_RESAMPLE_STRATIFIED, out,
+                         trace ? *trace : kNoTrace, kNoSmooth, M, bw_seeds, bw_out ? bw_out : &kNoBackward, reference);
 }
 
 int wsmc_debug_ssm_smooth(wsmc_ctx* c, int64_t* stats_out) {

@@ -398,6 +398,9 @@ struct wsmc_ctx {
     // the last backward pass (wsmc_debug_ssm_backward): the segments, the backward kernel, the rows kernel; its bytes
     int64_t ssm_bw_us[3] = {0, 0, 0}, ssm_bw_bytes = 0;
     int64_t ssm_bw_launches = 0;            // segments launched on the backward-recording kernels (cumulative)
+    // the last conditional batch (wsmc_debug_ssm_conditional): the segments, the backward kernel, the rows kernel; its bytes
+    int64_t ssm_cond_us[3] = {0, 0, 0}, ssm_cond_bytes = 0;
+    int64_t ssm_cond_launches = 0;          // segments launched on the conditional kernels (cumulative)
     bool timing = false;
     std::vector<hipEvent_t> events;
     wsmc_run_timing last_timing{};
@@ -1133,7 +1136,8 @@ struct SsmBatchGuidedArgs {   // both guided batch kernels (see SsmGuidedArgs)
     const SsmTarget* targ;    // [B][kSsmTargets]
 };
 // blocks of the variant that are resident on one CU (by registers, waves and LDS), and the device's CUs.
-// variant: 0 untraced, 1 traced, 2 recording, 3 guided, 4 guided recording, 5 backward recording, 6 guided backward recording
+// variant: 0 untraced, 1 traced, 2 recording, 3 guided, 4 guided recording, 5 backward recording, 6 guided backward recording,
+// 7 conditional
 hipError_t ssm_batch_occupancy(int device, unsigned feat, int variant, int threads, size_t lds, int* per_cu, int* cus);
 hipError_t launch_ssm_batch_segment(hipStream_t s, const SsmBatchArgs& a, unsigned feat, int threads);
 hipError_t launch_ssm_batch_segment_rec(hipStream_t s, const SsmBatchRecArgs& a, unsigned feat, int threads);
@@ -1149,6 +1153,13 @@ struct SsmBatchGuidedBwArgs {
     const SsmTarget* targ;    // [B][kSsmTargets]
 };
 hipError_t launch_ssm_batch_segment_bwrec(hipStream_t s, const SsmBatchBwRecArgs& a, unsigned feat, int threads);
+// a conditional batch (wsmc_ssm_run_conditional; csrc/wsmc_ssm_batch_conditional.hip): the backward-recording
+// batch's arguments, unchanged and first, and the filters' reference trajectories (occupancy variant 7)
+struct SsmBatchCondArgs {
+    SsmBatchBwRecArgs ra;
+    const double* ref;        // [B][T][S] written before the first launch and by nothing while a kernel runs
+};
+hipError_t launch_ssm_batch_segment_cond(hipStream_t s, const SsmBatchCondArgs& a, unsigned feat, int threads);
 hipError_t launch_ssm_batch_guided_segment_bwrec(hipStream_t s, const SsmBatchGuidedBwArgs& a, unsigned feat, int threads);
 // one handle over several devices (wsmc_multi.hip): the ABI entry points fan out
 int multi_destroy(wsmc_ctx* c);

@@ -31,6 +31,13 @@ namespace wsmc {
 // and through csrc/wsmc_ssm_batch_backward_rec.hip (WSMC_SSM_BWREC) and
 // csrc/wsmc_ssm_batch_guided_backward_rec.hip (with WSMC_SSM_GUIDED) for a batch that ends in backward
 // simulation: the trace point's columns and log-weights logged, no ancestors, as in csrc/wsmc_ssm.hip
+// and through csrc/wsmc_ssm_batch_conditional.hip (WSMC_SSM_COND over WSMC_SSM_BWREC) for a conditional
+// batch (wsmc_ssm_run_conditional): the backward-recording kernel with the reference trajectory pinned
+// into particle N - 1 after every SAMPLE of `step` and ss_resample's conditional branch. Kernels of
+// other names once more
+#if defined(WSMC_SSM_COND) && (!defined(WSMC_SSM_BWREC) || defined(WSMC_SSM_GUIDED) || defined(WSMC_SSM_SMOOTH))
+#error "WSMC_SSM_COND goes with WSMC_SSM_BWREC alone"
+#endif
 #if defined(WSMC_SSM_GUIDED)
 constexpr bool kSsbTraced = true, kSsbGuided = true;
 #if defined(WSMC_SSM_BWREC)
@@ -53,6 +60,12 @@ namespace {
 constexpr int kSsbVariantGamThreads = kSsGuidedGamThreads;
 typedef const SsmTarget __attribute__((address_space(4))) * SsTargetPtr;
 }
+#elif defined(WSMC_SSM_COND)
+constexpr bool kSsbTraced = true;
+#define WSMC_SSB_OCCUPANCY ssb_occupancy_cond
+#define WSMC_SSB_VARIANTS ssb_launch_cond
+#define WSMC_SSB_KERNEL k_ssm_batch_segment_cond
+typedef SsmBatchCondArgs SsbKernArgs;
 #elif defined(WSMC_SSM_BWREC)
 constexpr bool kSsbTraced = true;
 #define WSMC_SSB_OCCUPANCY ssb_occupancy_bwrec
@@ -85,6 +98,11 @@ typedef const SsmBatchFilter __attribute__((address_space(4))) * SsFilterPtr;
 constexpr bool kSsbGuided = false;
 constexpr int kSsbVariantGamThreads = kSsGamThreads;
 #endif
+#ifdef WSMC_SSM_COND
+constexpr bool kSsbCond = true;
+#else
+constexpr bool kSsbCond = false;
+#endif
 }
 
 // TR: the traced batch (wsmc_ssm_run_batch_traced), k_ssm_segment's flag
@@ -96,6 +114,10 @@ __global__ __launch_bounds__(THREADS) void WSMC_SSB_KERNEL(const SsmBatchGuidedB
 #elif defined(WSMC_SSM_GUIDED)
 __global__ __launch_bounds__(THREADS) void WSMC_SSB_KERNEL(const SsmBatchGuidedArgs ga) {
     const SsmBatchRecArgs& ka = ga.ra;
+    const SsmBatchArgs& a = ka.a;
+#elif defined(WSMC_SSM_COND)
+__global__ __launch_bounds__(THREADS) void WSMC_SSB_KERNEL(const SsmBatchCondArgs ca) {
+    const SsmBatchBwRecArgs& ka = ca.ra;
     const SsmBatchArgs& a = ka.a;
 #elif defined(WSMC_SSM_BWREC)
 __global__ __launch_bounds__(THREADS) void WSMC_SSB_KERNEL(const SsmBatchBwRecArgs ka) {
@@ -167,6 +189,13 @@ __global__ __launch_bounds__(THREADS) void WSMC_SSB_KERNEL(const SsmBatchArgs a)
 
     SsData dnext = dv;
     if (a.nsteps > 0) dnext = ss_row(data, dd, a.t0);
+#ifdef WSMC_SSM_COND
+    // filter b's reference trajectory [T][S], read as the data table is: the step's row a step ahead
+    static_assert(WSMC_SSM_MAX_COLS <= WSMC_SSM_MAX_DATA, "SsData holds a row of the reference");
+    const SsConstPtr ref = (SsConstPtr)ca.ref + b * (size_t)a.T * (size_t)S;
+    SsData rv = dv, rnext = dv;
+    if (a.nsteps > 0) rnext = ss_row(ref, S, a.t0);
+#endif
 
     // k_ssm_segment's loop: s = -1 is `init` (a fresh context: the op counter starts at 0)
     static_assert(offsetof(SsmBatchFilter, step) == offsetof(SsmBatchFilter, init) + WSMC_SSM_MAX_INIT * sizeof(SsmStmt),
@@ -180,6 +209,10 @@ __global__ __launch_bounds__(THREADS) void WSMC_SSB_KERNEL(const SsmBatchArgs a)
         if (!init) {
             dv = dnext;
             if (s + 1 < a.nsteps) dnext = ss_row(data, dd, t + 1);   // in flight during this step
+#ifdef WSMC_SSM_COND
+            rv = rnext;
+            if (s + 1 < a.nsteps) rnext = ss_row(ref, S, t + 1);
+#endif
         }
 #ifdef WSMC_SSM_SMOOTH
         int slot = t * ka.r.n_slots;   // the log's slot of the step's next Resample that can run
@@ -192,6 +225,10 @@ __global__ __launch_bounds__(THREADS) void WSMC_SSB_KERNEL(const SsmBatchArgs a)
             ss_statement<FEAT>(st, f.ins, L, dv, seed, op);
 #endif
             if (st.kind == WSMC_SSM_SAMPLE) {
+#ifdef WSMC_SSM_COND
+                // the pin: the owner of particle N - 1 overwrites the draw it has just stored
+                if (!init && L.i0 < N && L.i1 == N) L.cb[(size_t)ss_buf(L, st.col) * L.stride + (N - 1)] = ss_data(rv, st.col);
+#endif
                 op += 2;   // the draws, then a Resample that does not run (the weights have not changed)
             } else if (st.kind == WSMC_SSM_OBSERVE ||
                        (kSsbGuided && (st.kind == WSMC_SSM_WEIGHT || st.kind == WSMC_SSM_SAMPLE_IMPORTANCE))) {
@@ -206,7 +243,7 @@ __global__ __launch_bounds__(THREADS) void WSMC_SSB_KERNEL(const SsmBatchArgs a)
 #endif
                 if (row && (a.tr_mean || a.tr_var))
                     ss_trace_row(L, a.tr_mean ? a.tr_mean + r * S : nullptr, a.tr_var ? a.tr_var + r * S : nullptr);
-                const SsDecision d = ss_resample<TR>(L, K, a.ess_min, a.scheme, seed, op);
+                const SsDecision d = ss_resample<TR, kSsbCond>(L, K, a.ess_min, a.scheme, seed, op);
 #ifdef WSMC_SSM_SMOOTH
                 if (!init) {
                     if (d.resampled) ss_record_anc(L, alog + (size_t)slot * N, ranf + slot);
@@ -316,6 +353,8 @@ hipError_t WSMC_SSB_VARIANTS(hipStream_t s, const SsbKernArgs& a, unsigned feat,
 }
 
 #if !defined(WSMC_SSM_TRACED) && !defined(WSMC_SSM_SMOOTH) && !defined(WSMC_SSM_GUIDED) && !defined(WSMC_SSM_BWREC)
+hipError_t ssb_occupancy_cond(unsigned feat, int threads, size_t lds, int* per_cu);           // csrc/wsmc_ssm_batch_conditional.hip
+hipError_t ssb_launch_cond(hipStream_t s, const SsmBatchCondArgs& a, unsigned feat, int threads, size_t lds, int B);
 hipError_t ssb_occupancy_bwrec(unsigned feat, int threads, size_t lds, int* per_cu);          // csrc/wsmc_ssm_batch_backward_rec.hip
 hipError_t ssb_launch_bwrec(hipStream_t s, const SsmBatchBwRecArgs& a, unsigned feat, int threads, size_t lds, int B);
 hipError_t ssb_occupancy_guided_bwrec(unsigned feat, int threads, size_t lds, int* per_cu);   // csrc/wsmc_ssm_batch_guided_backward_rec.hip
@@ -332,6 +371,7 @@ hipError_t ssb_launch_rec(hipStream_t s, const SsmBatchRecArgs& a, unsigned feat
 hipError_t ssm_batch_occupancy(int device, unsigned feat, int variant, int threads, size_t lds, int* per_cu, int* cus) {
     const hipError_t e = hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, device);
     if (e != hipSuccess) return e;
+    if (variant == 7) return ssb_occupancy_cond(feat, threads, lds, per_cu);
     if (variant == 6) return ssb_occupancy_guided_bwrec(feat, threads, lds, per_cu);
     if (variant == 5) return ssb_occupancy_bwrec(feat, threads, lds, per_cu);
     if (variant == 4) return ssb_occupancy_guided_rec(feat, threads, lds, per_cu);
@@ -376,6 +416,12 @@ hipError_t launch_ssm_batch_guided_segment_bwrec(hipStream_t s, const SsmBatchGu
     const SsmBatchArgs& ba = a.ra.a;
     if (!ssb_segment_ok(ba, feat, threads, true) || !a.targ || !a.ra.r.hist || !a.ra.r.lwlog || a.ra.r.T != ba.T) return hipErrorInvalidValue;
     return ssb_launch_guided_bwrec(s, a, feat, threads, ssm_lds_bytes(ba.N, ba.S), ba.B);
+}
+
+hipError_t launch_ssm_batch_segment_cond(hipStream_t s, const SsmBatchCondArgs& a, unsigned feat, int threads) {
+    const SsmBatchArgs& ba = a.ra.a;
+    if (!ssb_segment_ok(ba, feat, threads) || !a.ref || !a.ra.r.hist || !a.ra.r.lwlog || a.ra.r.T != ba.T) return hipErrorInvalidValue;
+    return ssb_launch_cond(s, a, feat, threads, ssm_lds_bytes(ba.N, ba.S), ba.B);
 }
 #endif
 

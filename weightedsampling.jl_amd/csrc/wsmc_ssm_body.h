@@ -222,8 +222,10 @@ struct SsDecision {
 // Resample on the block's log-weights (wsmc_lgssm.hip's, its arithmetic unchanged): the ESS and
 // the strict decision; a resampling step gathers every column and resets the weights to the
 // log-mean. Every thread calls it (it holds barriers). op: the Resample's op counter. TR: a traced
-// run, whose first wave also finishes the evidence from the sums it holds.
-template <bool TR>
+// run, whose first wave also finishes the evidence from the sums it holds. COND (the conditional
+// kernels alone): the ancestors are N independent draws with slot N - 1 forced to N - 1
+// (wsmc_ssm_run_conditional), `scheme` is not read.
+template <bool TR, bool COND = false>
 __device__ inline SsDecision ss_resample(SsState& L, int K, double ess_min, int scheme, uint64_t seed, uint64_t op) {
     const int N = L.N, i0 = L.i0, i1 = L.i1, lane = L.lane, wave = L.wave, nw = L.nw;
     uint64_t* red0 = L.red;
@@ -311,50 +313,78 @@ __device__ inline SsDecision ss_resample(SsState& L, int K, double ess_min, int 
     __syncthreads();
     uint64_t excl = incl - run;
     for (int w = 0; w < wave; ++w) excl += red0[w];
-    // rank of each particle's CDF end: its slots are [rank(C_{m-1}), rank(C_m)); the rank goes
-    // into the low word of the particle's own CDF entry (no other thread reads that entry)
-    const double ratio = wsmc_u64_to_d((uint64_t)N) / wsmc_u64_to_d(Q);
-    for (int i = i0; i < i1; ++i) {
-        const uint64_t C = cdf[i] + excl;
-        const uint64_t rk = wsmc_rank_r(C, Q, (uint64_t)N, ratio, scheme, seed, op, 0);
-        reinterpret_cast<int32_t*>(cdf + i)[0] = (int32_t)rk;
-        L.anc[i] = 0;
-    }
-    __syncthreads();
-    // marks: particle m writes m at its first slot (the slot ranges partition [0, N))
-    for (int i = i0; i < i1; ++i) {
-        const int lo = i ? reinterpret_cast<const int32_t*>(cdf + (i - 1))[0] : 0;
-        const int hi = reinterpret_cast<const int32_t*>(cdf + i)[0];
-        if (lo < hi && lo < N) L.anc[lo] = i;
-    }
-    __syncthreads();
-    // inclusive max-scan of the marks: the ancestors
-    int rmax = 0;
-    for (int i = i0; i < i1; ++i) { const int v = L.anc[i]; rmax = v > rmax ? v : rmax; }
-    int imax = rmax;
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(imax, d, 64);
-        if (lane >= d) imax = o > imax ? o : imax;
-    }
-    if (lane == 63) red1[wave] = (uint64_t)(uint32_t)imax;   // (red1's readers: two barriers back)
-    int before = __shfl_up(imax, 1, 64);
-    if (lane == 0) before = 0;
-    __syncthreads();
-    for (int w = 0; w < wave; ++w) {
-        const int o = (int)(uint32_t)red1[w];
-        before = o > before ? o : before;
-    }
-    // the ancestors, the weight reset and column 0's gather into the spare (the ranks in it were
-    // last read before the marks' barrier), each new particle written by its owner
-    {
+    if constexpr (COND) {
+        // the full C_i in place of the thread-local sums; then slot j is wsmc_sample_particles(N,
+        // replace)'s draw j: the smallest m with C_m > its target (C_{N-1} = Q is above every target)
+        for (int i = i0; i < i1; ++i) cdf[i] += excl;
+        __syncthreads();
+        for (int i = i0; i < i1; ++i) {
+            int lo = N - 1;
+            if (i < N - 1) {
+                const uint64_t x = wsmc_multi_target(wsmc_multi_word(seed, op, (uint64_t)i), Q);
+                lo = 0;
+                for (int hi = N - 1; lo < hi;) {
+                    const int mid = (lo + hi) >> 1;
+                    if (cdf[mid] > x) hi = mid; else lo = mid + 1;
+                }
+            }
+            L.anc[i] = lo;
+        }
+        // the weight reset and column 0's gather into the spare, which holds the CDF: behind the
+        // last search of any thread
+        __syncthreads();
         const double* src = L.cb + ss_buf(L, 0) * L.stride;
         double* dst = reinterpret_cast<double*>(cdf);
         for (int i = i0; i < i1; ++i) {
-            const int v = L.anc[i];
-            before = v > before ? v : before;
-            L.anc[i] = before;
-            dst[i] = src[before];
+            dst[i] = src[L.anc[i]];
             L.lw[i] = mean;
+        }
+    } else {
+        // rank of each particle's CDF end: its slots are [rank(C_{m-1}), rank(C_m)); the rank goes
+        // into the low word of the particle's own CDF entry (no other thread reads that entry)
+        const double ratio = wsmc_u64_to_d((uint64_t)N) / wsmc_u64_to_d(Q);
+        for (int i = i0; i < i1; ++i) {
+            const uint64_t C = cdf[i] + excl;
+            const uint64_t rk = wsmc_rank_r(C, Q, (uint64_t)N, ratio, scheme, seed, op, 0);
+            reinterpret_cast<int32_t*>(cdf + i)[0] = (int32_t)rk;
+            L.anc[i] = 0;
+        }
+        __syncthreads();
+        // marks: particle m writes m at its first slot (the slot ranges partition [0, N))
+        for (int i = i0; i < i1; ++i) {
+            const int lo = i ? reinterpret_cast<const int32_t*>(cdf + (i - 1))[0] : 0;
+            const int hi = reinterpret_cast<const int32_t*>(cdf + i)[0];
+            if (lo < hi && lo < N) L.anc[lo] = i;
+        }
+        __syncthreads();
+        // inclusive max-scan of the marks: the ancestors
+        int rmax = 0;
+        for (int i = i0; i < i1; ++i) { const int v = L.anc[i]; rmax = v > rmax ? v : rmax; }
+        int imax = rmax;
+        for (int d = 1; d < 64; d <<= 1) {
+            const int o = __shfl_up(imax, d, 64);
+            if (lane >= d) imax = o > imax ? o : imax;
+        }
+        if (lane == 63) red1[wave] = (uint64_t)(uint32_t)imax;   // (red1's readers: two barriers back)
+        int before = __shfl_up(imax, 1, 64);
+        if (lane == 0) before = 0;
+        __syncthreads();
+        for (int w = 0; w < wave; ++w) {
+            const int o = (int)(uint32_t)red1[w];
+            before = o > before ? o : before;
+        }
+        // the ancestors, the weight reset and column 0's gather into the spare (the ranks in it were
+        // last read before the marks' barrier), each new particle written by its owner
+        {
+            const double* src = L.cb + ss_buf(L, 0) * L.stride;
+            double* dst = reinterpret_cast<double*>(cdf);
+            for (int i = i0; i < i1; ++i) {
+                const int v = L.anc[i];
+                before = v > before ? v : before;
+                L.anc[i] = before;
+                dst[i] = src[before];
+                L.lw[i] = mean;
+            }
         }
     }
     // column k > 0 into the buffer column k - 1 has just left: a barrier first, other threads

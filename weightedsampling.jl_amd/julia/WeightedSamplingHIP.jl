@@ -1189,4 +1189,69 @@ function debug_ssm_backward(state::HipState)
     return (segments_us=st[1], backward_us=st[2], rows_us=st[3], bytes=st[4], recording_segments=st[5])
 end
 
+"""
+    ssm_spec_conditional(spec) -> Vector{Int}
+
+The columns of `spec` (1-based) a conditional run pins to its reference trajectory: those a SAMPLE
+of the step writes (`wsmc_ssm_spec_conditional`); throws with the library's reason for a spec a
+conditional run is not defined for (an importance SAMPLE or a WEIGHT, an OBSERVE in `init`,
+anything `ssm_spec_backward` refuses).
+"""
+function ssm_spec_conditional(spec::WsmcSsmSpec)
+    pin = zeros(Int32, 4)   # WSMC_SSM_MAX_COLS
+    check(ccall((:wsmc_ssm_spec_conditional, libwsmc), Cint, (Ref{WsmcSsmSpec}, Ptr{Int32}), spec, pin))
+    return findall(!=(0), pin)
+end
+
+"""
+    ssm_run_conditional(state, specs, data, n, seeds, reference, M, bw_seeds)
+
+B conditional SMC filters in one call (`wsmc_ssm_run_conditional`): filter b runs with particle n
+pinned to `reference[:, :, b]` (n_cols x T x B) and independent ancestor draws with the last slot
+forced, then draws M backward trajectories over its record with `bw_seeds[b]`: with M = 1 one
+particle-Gibbs sweep, whose `paths` are the next sweep's reference. Returns `ssm_run_batch_backward`'s
+named tuple; with M = 0 no backward pass runs and `bw_seeds` may be empty. `state` gives the device,
+the stream and `ess_perc_min`.
+"""
+function ssm_run_conditional(state::HipState, specs, data, n::Integer, seeds::AbstractVector{<:Integer},
+                             reference::Array{Float64,3}, M::Integer, bw_seeds::AbstractVector{<:Integer})
+    B = length(seeds)
+    M == 0 || length(bw_seeds) == B || throw(ArgumentError("one backward seed per filter"))
+    sp = specs isa WsmcSsmSpec ? [specs] : collect(WsmcSsmSpec, specs)
+    tabs = data isa AbstractVector{<:AbstractVecOrMat} ? collect(data) : [data]
+    length(sp) in (1, B) && length(tabs) in (1, B) || throw(ArgumentError("one spec / table, or one per filter"))
+    T = size(tabs[1], 1)
+    all(t -> size(t, 1) == T, tabs) || throw(ArgumentError("the filters' tables must have one length"))
+    S = Int(sp[1].n_cols)
+    size(reference) == (S, T, B) || throw(ArgumentError("reference: n_cols x T x B"))
+    rowmajor(t) = Vector{Float64}(vec(permutedims(reshape(Float64.(t), T, :))))
+    d = reduce(vcat, rowmajor.(tabs))
+    ev = Vector{Float64}(undef, B); nres = Vector{Int64}(undef, B); last = Vector{Int32}(undef, B)
+    b = _bw_buffers(T, S, n, M, B)
+    sd = Vector{UInt64}(seeds .% UInt64); bsd = Vector{UInt64}(bw_seeds .% UInt64)
+    GC.@preserve ev nres last b begin
+        out = WsmcSsmBatchOut(pointer(ev), C_NULL, C_NULL, C_NULL, C_NULL, pointer(nres), pointer(last))
+        bo = M == 0 ? WsmcSsmBackwardOut(C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL) :
+             WsmcSsmBackwardOut(pointer(b.idx), pointer(b.paths), pointer(b.mean), pointer(b.var), C_NULL, C_NULL)
+        check(ccall((:wsmc_ssm_run_conditional, libwsmc), Cint,
+                    (Ptr{Cvoid}, Ptr{WsmcSsmSpec}, Int32, Ptr{Float64}, Int32, Int32, Int32, Int32, Ptr{UInt64},
+                     Float64, Ptr{Float64}, Ref{WsmcSsmBatchOut}, Ptr{Cvoid}, Int32, Ptr{UInt64}, Ref{WsmcSsmBackwardOut}),
+                    state.store.ctx, sp, length(sp), isempty(d) ? C_NULL : d, length(tabs), T, n, B, sd,
+                    state.ess_perc_min, reference, out, C_NULL, M, M == 0 ? C_NULL : bsd, bo))
+    end
+    return (; log_evidence=ev, n_resamples=nres, last_resampled=last .!= 0, b...)
+end
+
+"""
+    debug_ssm_conditional(state)
+
+`wsmc_debug_ssm_conditional`: the last conditional batch's device microseconds (its segments, the
+backward kernel, the rows kernel), its bytes, and the segments launched on the conditional kernels.
+"""
+function debug_ssm_conditional(state::HipState)
+    st = zeros(Int64, 5)
+    check(ccall((:wsmc_debug_ssm_conditional, libwsmc), Cint, (Ptr{Cvoid}, Ptr{Int64}), state.store.ctx, st))
+    return (segments_us=st[1], backward_us=st[2], rows_us=st[3], bytes=st[4], conditional_segments=st[5])
+end
+
 end # module

@@ -16,13 +16,13 @@ from .dsl import (Bernoulli, BernoulliLogit, Beta, Binomial, Cauchy, Chisq, Col,
 from . import dsl
 from . import ssm
 from .dsl import Data
-from .ssm import SSM, SsmBackward, SsmRecord, SsmSmooth, SsmTrace
+from .ssm import SSM, SsmBackward, SsmFinal, SsmRecord, SsmSmooth, SsmTrace, particle_gibbs, pg_seeds
 from . import models
 from .transformers import (Assign, Cond, FusedSSM2D, HipColumnStore, ImportanceKernel, Loop, Move, Observe,
                            Resample, RW, Sample, Sequence, SMCState, Weight, apply, autoRW, dataframe, describe,
                            expectation, importance_kernel, marginal_diversity, resampled, run, sample, score_logpdf)
 
-__all__ = ["abi", "dsl", "ssm", "SSM", "SsmBackward", "SsmRecord", "SsmSmooth", "SsmTrace", "Data", "Context", "device_count", "Col", "Expr", "Fx", "Bernoulli", "BernoulliLogit", "Cauchy", "Exponential", "Geometric", "Gumbel",
+__all__ = ["abi", "dsl", "ssm", "SSM", "SsmBackward", "SsmFinal", "SsmRecord", "particle_gibbs", "pg_seeds", "SsmSmooth", "SsmTrace", "Data", "Context", "device_count", "Col", "Expr", "Fx", "Bernoulli", "BernoulliLogit", "Cauchy", "Exponential", "Geometric", "Gumbel",
            "Laplace", "Logistic", "LogNormal", "Rayleigh", "Gamma", "InverseGamma", "Chisq", "Beta", "TDist", "Poisson", "Binomial",
            "NegativeBinomial", "Kernel", "Normal", "MvNormal", "HalfNormal",
            "Uniform", "Oscillator", "models", "load_library", "WSMCError", "RESAMPLE_STRATIFIED",

@@ -238,6 +238,11 @@ SIGNATURES = {
                                               C.POINTER(C.c_uint64), C.c_double, C.c_int32, C.POINTER(SsmBatchOut),
                                               C.POINTER(SsmTraceOut), C.c_int32, C.POINTER(C.c_uint64), C.POINTER(SsmBackwardOut)]),
     "wsmc_debug_ssm_backward": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "wsmc_ssm_spec_conditional": (C.c_int, [C.POINTER(SsmSpec), _I32P]),
+    "wsmc_ssm_run_conditional": (C.c_int, [_P, C.POINTER(SsmSpec), C.c_int32, _D, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                           C.POINTER(C.c_uint64), C.c_double, _D, C.POINTER(SsmBatchOut),
+                                           C.POINTER(SsmTraceOut), C.c_int32, C.POINTER(C.c_uint64), C.POINTER(SsmBackwardOut)]),
+    "wsmc_debug_ssm_conditional": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "wsmc_run_set_timing": (C.c_int, [_P, C.c_int32]),
     "wsmc_run_get_timing": (C.c_int, [_P, C.POINTER(RunTiming)]),
     "wsmc_debug_kernel_bench": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _D]),

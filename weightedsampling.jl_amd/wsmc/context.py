@@ -15,7 +15,7 @@ import numpy as np
 
 from . import abi
 from .abi import Dist, Operand, RunTiming, State, check, load_library
-from .ssm import (TRACE_PARTS, SsmSmooth, SsmTrace, backward_buffers, backward_by_name, batch_arguments, smooth_buffers,
+from .ssm import (TRACE_PARTS, SsmRecord, SsmSmooth, SsmTrace, backward_buffers, backward_by_name, batch_arguments, smooth_buffers,
                   smooth_by_name, smooth_parts, trace_buffers, trace_by_name, trace_parts)
 
 _D = C.POINTER(C.c_double)
@@ -665,6 +665,85 @@ class Context:
         if state:
             res.cols = {name: cols[:, k, :] for k, name in enumerate(first.cols)}
         return res
+
+    def ssm_run_conditional(self, specs, data, n: int, seeds, reference, ess_perc_min=0.5, trace: bool = False,
+                            backward: int = 0, backward_seeds=None, record: bool = False, state: bool = False,
+                            T: int | None = None) -> "SsmBatchResult":
+        """B = len(seeds) conditional SMC filters in one call (wsmc_ssm_run_conditional), one
+        persistent workgroup each: filter b is, bit for bit, spec.conditional_definition(make_backend,
+        table b, n, seeds[b], reference[b], ess_perc_min) with particle n-1 pinned to its reference
+        trajectory and independent ancestor draws with the last slot forced. reference: an array
+        [B, T, n_cols] in the spec's column order, or column name -> [B, T] (entries of columns
+        that are not pinned are ignored). specs, data, trace and state as in ssm_run_batch, whose
+        SsmBatchResult this returns. backward=M with backward_seeds [B] fills `backward`, a list of
+        B SsmBackward drawn over each filter's record (with record=True the record itself); with
+        backward=0 and record=True `backward` holds B SsmRecord. One sweep of particle Gibbs with
+        backward sampling is this call with backward=1 (wsmc.particle_gibbs)."""
+        M = int(backward)
+        if M < 0 or (M and (backward_seeds is None or len(backward_seeds) != len(seeds))):
+            raise ValueError("backward: the number of trajectories, and one backward seed per filter")
+        spec_list, tabs, seeds_a = batch_arguments(specs, data, n, seeds, T)   # (before any device call)
+        B, first, steps = len(seeds_a), spec_list[0], len(tabs[0])
+        S, n = len(first.cols), int(n)
+        if isinstance(reference, dict):
+            reference = {k: np.asarray(v, dtype=np.float64).reshape(B, steps) for k, v in reference.items()}
+            ref = np.stack([first.reference_table({k: v[b] for k, v in reference.items()}, steps) for b in range(B)])
+        else:
+            ref = np.ascontiguousarray(np.asarray(reference, dtype=np.float64))
+            if ref.shape != (B, steps, S):
+                raise ValueError(f"reference: shape {ref.shape}, the call has {B} filters of {steps} steps of {S} columns")
+        tab = np.ascontiguousarray(np.stack(tabs)) if tabs[0].size else None
+        arr = (abi.SsmSpec * len(spec_list))()
+        for k, s in enumerate(spec_list):
+            C.memmove(C.byref(arr[k]), C.byref(s.spec), C.sizeof(abi.SsmSpec))
+        res = SsmBatchResult()
+        res.log_evidence = np.empty(B)
+        res.n_resamples = np.empty(B, dtype=np.int64)
+        res.last_resampled = np.empty(B, dtype=np.int32)
+        out = abi.SsmBatchOut()
+        out.log_evidence = _dptr(res.log_evidence)
+        out.n_resamples = res.n_resamples.ctypes.data_as(C.POINTER(C.c_int64))
+        out.last_resampled = res.last_resampled.ctypes.data_as(_I32P)
+        tbuf, tr = trace_buffers(TRACE_PARTS if trace else (), (B, steps), S)
+        if state:
+            cols = np.empty((B, S, n))
+            res.log_weights = np.empty((B, n))
+            res.last_ancestors = np.empty((B, n), dtype=np.int32)
+            out.cols = _dptr(cols)
+            out.log_weights = _dptr(res.log_weights)
+            out.last_ancestors = res.last_ancestors.ctypes.data_as(_I32P)
+        if M:
+            bbuf, bo = backward_buffers(steps, S, n, M, lead=(B,), record=record)
+            bseeds = np.ascontiguousarray(np.asarray([int(s) & (2**64 - 1) for s in backward_seeds], dtype=np.uint64))
+        else:   # the record alone, if asked for
+            bbuf = {"particles": np.empty((B, steps, S, n)), "log_weights": np.empty((B, steps, n))} if record else {}
+            bo, bseeds = abi.SsmBackwardOut(), None
+            for p, a in bbuf.items():
+                setattr(bo, p, _dptr(a))
+        check(self._L.wsmc_ssm_run_conditional(
+            self._h, arr, len(spec_list), _dptr(tab) if tab is not None else None, len(tabs), steps, n, B,
+            seeds_a.ctypes.data_as(C.POINTER(C.c_uint64)), float(ess_perc_min), _dptr(ref), C.byref(out), C.byref(tr), M,
+            bseeds.ctypes.data_as(C.POINTER(C.c_uint64)) if M else None, C.byref(bo)))
+        if M:
+            res.backward = [backward_by_name({k: v[b] for k, v in bbuf.items()}, first.cols) for b in range(B)]
+        elif record:
+            res.backward = [SsmRecord(bbuf["particles"][b], bbuf["log_weights"][b]) for b in range(B)]
+        if trace:
+            res.ess, res.mean, res.var, res.log_evidence_trace = trace_by_name(tbuf, first.cols)
+        res.last_resampled = res.last_resampled.astype(bool)
+        if state:
+            res.cols = {name: cols[:, k, :] for k, name in enumerate(first.cols)}
+        return res
+
+    def ssm_conditional_stats(self) -> dict:
+        """wsmc_debug_ssm_conditional's figures of the last conditional batch on this context: device
+        seconds of its segments, of the backward kernel and of the rows kernel, the bytes of the record,
+        the references and the outputs, and the segments this context has launched on the conditional
+        kernels (cumulative; no other run launches them)."""
+        st = (C.c_int64 * 5)()
+        check(self._L.wsmc_debug_ssm_conditional(self._h, st))
+        return {"segments_s": st[0] / 1e6, "backward_s": st[1] / 1e6, "rows_s": st[2] / 1e6, "bytes": int(st[3]),
+                "conditional_segments": int(st[4])}
 
     def ssm_smooth_stats(self) -> dict:
         """wsmc_debug_ssm_smooth's figures of the last smoothed run or batch on this context: device

@@ -729,3 +729,231 @@ class SSM:
             be.close()
         return SsmBackward(idx, {c: paths[:, k, :] for k, c in enumerate(self.cols)}, _by_name(mean, self.cols),
                            _by_name(var, self.cols), record)
+
+    # ---- conditional SMC (particle Gibbs) ----
+    def conditional_terms(self) -> list:
+        """The columns a conditional run pins to its reference trajectory, by name in the spec's
+        order: wsmc_ssm_spec_conditional's rule, restated here. They are the columns a SAMPLE of
+        `step` writes. Raises ValueError with the library's reason for a spec a conditional run is
+        not defined for: one with an importance SAMPLE or a WEIGHT (pinning an importance Sample
+        needs its weight term at the pinned value), one whose `init` holds anything but SAMPLE and
+        assignments, and everything backward_terms refuses."""
+        self.check()
+        sp = self.spec
+        for where, stmts, n in (("init", sp.init, sp.n_init), ("step", sp.step, sp.n_step)):
+            for q in range(n):
+                kind = stmts[q].kind
+                if kind == abi.SSM_SAMPLE_IMPORTANCE:
+                    raise ValueError(f"ssm conditional: statement {q} of {where} is an importance SAMPLE (pinning it needs its "
+                                     "weight term at the pinned value)")
+                if kind == abi.SSM_WEIGHT:
+                    raise ValueError(f"ssm conditional: statement {q} of {where} is a WEIGHT (guided specs are not supported)")
+                if where == "init" and kind == abi.SSM_OBSERVE:
+                    raise ValueError(f"ssm conditional: statement {q} of init is an OBSERVE (init may hold SAMPLE and "
+                                     "assignments only: it is not pinned)")
+        try:
+            self.backward_terms()
+        except ValueError as e:
+            raise ValueError(f"ssm conditional: {e}") from None
+        drawn = {int(sp.step[q].col) for q in range(sp.n_step) if sp.step[q].kind == abi.SSM_SAMPLE}
+        return [c for k, c in enumerate(self.cols) if k in drawn]
+
+    def reference_table(self, reference, T: int) -> np.ndarray:
+        """a conditional run's reference trajectory as the [T, n_cols] table the C entry point
+        takes: an array of that shape, or column name -> [T] (a column that is not given is 0.0;
+        entries of columns that are not pinned are ignored)"""
+        S = len(self.cols)
+        if isinstance(reference, dict):
+            ref = np.zeros((int(T), S))
+            for name, v in reference.items():
+                ref[:, self.cols.index(name)] = np.asarray(v, dtype=np.float64).reshape(int(T))
+            return ref
+        ref = np.ascontiguousarray(np.asarray(reference, dtype=np.float64))
+        if ref.shape != (int(T), S):
+            raise ValueError(f"reference: shape {ref.shape}, the run has {T} steps of {S} columns")
+        return ref
+
+    def conditional_definition(self, make_backend, data, n: int, seed: int, reference, ess_perc_min: float,
+                               T: int | None = None, trace: bool = False):
+        """Conditional SMC, operator by operator: the definition of what Context.ssm_run_conditional
+        computes for one filter. make_backend(n, seed) gives a fresh context (a Context or the
+        tests' Oracle). It is statements(..., record=True) with two changes; particle n-1 is the
+        reference particle.
+        Pin: in `step` (never in `init`), right after a `sample` of step t, col_download of its
+        column, the last entry set to reference[t][column], col_upload.
+        Conditional Resample, in place of every Resample: read get_state()'s op counter r,
+        weights_download() and every column; resample(ess_perc_min, STRATIFIED, wait=True); if it
+        ran (get_state()'s n_resamples grew: a Resample that meets unchanged weights, as after a
+        `sample`, does nothing and reports the previous flag), upload the saved weights to a scratch backend of the same n and seed,
+        set_op_counter(r) and idx = sample_particles(n, True) there; idx[n-1] = n-1;
+        col_upload(k, saved[k][idx]) for every column. So the decision, the ESS, the evidence and
+        the reset weights are the ordinary Resample's and the ancestors are n independent draws
+        with the last slot forced.
+        Returns (flags, ESS%, SsmRecord, SsmFinal), with trace=True (flags, ESS%, SsmTrace,
+        SsmRecord, SsmFinal)."""
+        self.conditional_terms()
+        sp = self.spec
+        tab = self.table(data, T)
+        T, S, n = len(tab), len(self.cols), int(n)
+        ref = self.reference_table(reference, T)
+        be = make_backend(n, seed)
+        ids = [be.col_create(name, 1) for name in self.cols]
+        end = SsmFinal(None, None, np.zeros(n, dtype=np.int32), 0, None)
+
+        def resample():
+            before = be.get_state()
+            r = before["op_counter"]
+            w = be.weights_download()
+            saved = [be.col_download(i) for i in ids]
+            ran, ess = be.resample(ess_perc_min, abi.RESAMPLE_STRATIFIED, wait=True)
+            if be.get_state()["n_resamples"] > before["n_resamples"]:
+                scratch = make_backend(n, seed)
+                scratch.weights_upload(w)
+                scratch.set_op_counter(r)
+                idx = np.asarray(scratch.sample_particles(n, True), dtype=np.int64)
+                if hasattr(scratch, "close"):
+                    scratch.close()
+                idx[n - 1] = n - 1
+                for i, v in zip(ids, saved):
+                    be.col_upload(i, v[idx])
+                end.last_ancestors = idx.astype(np.int32)
+                end.n_resamples += 1
+            return bool(ran), float(ess)
+
+        def prepare(s):
+            """(kind, column, the folded parts, patch) of a statement"""
+            patch = []
+            if s.kind == abi.SSM_SAMPLE:
+                parts = (_fold_dist(s.dist, ids, patch),)
+            elif s.kind == abi.SSM_ASSIGN:
+                parts = ([_fold_operand(s.value, ids, patch)],)
+            elif s.kind == abi.SSM_ASSIGN_EXPR:
+                parts = _fold_prog(s, ids, patch)
+            else:
+                parts = (_fold_dist(s.dist, ids, patch), [_fold_operand(s.value, ids, patch)])
+            return int(s.kind), int(s.col), parts, patch
+
+        def issue(kind, col, parts, pin=None, at=None):
+            """the statement, then its Resample's (flag, ESS%) if it has one"""
+            if kind == abi.SSM_SAMPLE:
+                be.sample(ids[col], parts[0])
+                if pin is not None:
+                    v = be.col_download(ids[col])
+                    v[n - 1] = pin[col]
+                    be.col_upload(ids[col], v)
+                return resample()
+            if kind == abi.SSM_ASSIGN:
+                be.assign(ids[col], parts[0])
+            elif kind == abi.SSM_ASSIGN_EXPR:
+                be.assign_expr(ids[col], parts[0], parts[1])
+            else:
+                be.observe(parts[0], parts[1])
+                if at is not None:
+                    at()
+                return resample()
+            return None
+
+        for q in range(sp.n_init):
+            kind, col, parts, _ = prepare(sp.init[q])
+            issue(kind, col, parts)
+        step = [prepare(sp.step[q]) for q in range(sp.n_step)]
+        last = sp.n_step - 1   # (conditional_terms: the step ends in its last OBSERVE)
+        flags, ess = [], []
+        mean, var, lev = np.empty((T, S)), np.empty((T, S)), np.empty(T)
+        exprs = [Operand.column(i) for i in ids]
+        rec_cols, rec_lw = [], []
+
+        def point(t):
+            if trace:
+                m, cv = be.weighted_moments(exprs)
+                mean[t], var[t] = m, np.diagonal(cv)
+                lev[t] = be.log_evidence()
+            rec_cols.append(np.stack([be.col_download(i) for i in ids]))
+            rec_lw.append(be.weights_download())
+
+        for t in range(T):
+            row = tab[t]
+            for q, (kind, col, parts, patch) in enumerate(step):
+                for obj, field, j in patch:
+                    setattr(obj, field, row[j])
+                r = issue(kind, col, parts, pin=ref[t], at=(lambda: point(t)) if q == last else None)
+                if q == last:
+                    flags.append(r[0])
+                    ess.append(r[1])
+                    end.last_resampled = r[0]
+        end.cols = {c: be.col_download(ids[k]) for k, c in enumerate(self.cols)}
+        end.log_weights = be.weights_download()
+        end.log_evidence = be.log_evidence()
+        if hasattr(be, "close"):
+            be.close()
+        out = (flags, np.array(ess))
+        if trace:
+            out = out + (SsmTrace(np.array(ess), _by_name(mean, self.cols), _by_name(var, self.cols), lev),)
+        return out + (SsmRecord(np.stack(rec_cols), np.stack(rec_lw)), end)
+
+
+class SsmFinal:
+    """What a filter leaves at its end (SSM.conditional_definition's last member; row b of
+    Context.ssm_run_conditional(state=True)'s arrays): `cols` (name -> [n]), `log_weights` [n],
+    `last_ancestors` [n] int32 (the ancestors of the last Resample that ran, zeros if none did),
+    `n_resamples`, `log_evidence` and `last_resampled`, the decision of the last step's last Resample."""
+
+    def __init__(self, cols, log_weights, last_ancestors, n_resamples, log_evidence, last_resampled=False):
+        self.cols, self.log_weights, self.last_ancestors = cols, log_weights, last_ancestors
+        self.n_resamples, self.log_evidence, self.last_resampled = n_resamples, log_evidence, last_resampled
+
+
+_M64 = 2**64 - 1
+
+
+def pg_seeds(seed: int, sweep: int, chains: int):
+    """The seeds of particle_gibbs' sweep `sweep`: (seeds, bw_seeds), [chains] uint64 each, the
+    filters' and their backward passes'. A pure function: seed number i = 2 (sweep chains + b) +
+    role (role 0 the filter's, 1 the backward pass's, b the chain) is the splitmix64 output
+    mix(seed + (i + 1) 0x9E3779B97F4A7C15 mod 2^64), mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9;
+    z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31. mix is a bijection and the multiplier is
+    odd, so for one seed and one chain count the values are distinct across sweeps, chains and the
+    two roles."""
+    def mix(z):
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+        return z ^ (z >> 31)
+
+    out = np.empty((2, int(chains)), dtype=np.uint64)
+    for b in range(int(chains)):
+        for role in range(2):
+            i = 2 * (int(sweep) * int(chains) + b) + role
+            out[role, b] = mix((int(seed) + (i + 1) * 0x9E3779B97F4A7C15) & _M64)
+    return out[0], out[1]
+
+
+def particle_gibbs(ctx, spec, data, n: int, sweeps: int, seed: int, chains: int = 1, ess_perc_min: float = 0.5,
+                   reference=None):
+    """Particle Gibbs with backward sampling for a fixed spec, one device call a sweep. Sweep 0 is
+    ctx.ssm_run_batch(backward=1) (an unconditional filter and one backward trajectory per chain)
+    unless `reference` ([chains, T, n_cols], or name -> [chains, T]) starts the chains; every later
+    sweep is one ctx.ssm_run_conditional(backward=1) on the previous sweep's trajectories, whose
+    backward paths become the next reference. Sweep j draws from pg_seeds(seed, j, chains).
+    Returns (trajectories, log_evidence): column name -> [sweeps, chains, T], and [sweeps, chains],
+    each sweep's filter's log evidence estimate. The spec's numbers are the caller's to change
+    between calls (a parameter update); within one call they are fixed."""
+    sweeps, chains = int(sweeps), int(chains)
+    if sweeps < 1 or chains < 1:
+        raise ValueError("particle_gibbs: at least one sweep and one chain")
+    T, S = len(spec.table(data)), len(spec.cols)
+    traj = np.empty((sweeps, chains, T, S))
+    logev = np.empty((sweeps, chains))
+    ref = None
+    if reference is not None:
+        ref = np.stack([spec.reference_table({k: np.asarray(v)[b] for k, v in reference.items()} if isinstance(reference, dict)
+                                             else np.asarray(reference)[b], T) for b in range(chains)])
+    for j in range(sweeps):
+        seeds, bw_seeds = pg_seeds(seed, j, chains)
+        if ref is None:
+            res = ctx.ssm_run_batch(spec, data, n, seeds, ess_perc_min=ess_perc_min, backward=1, backward_seeds=bw_seeds)
+        else:
+            res = ctx.ssm_run_conditional(spec, data, n, seeds, ref, ess_perc_min=ess_perc_min, backward=1,
+                                          backward_seeds=bw_seeds)
+        ref = np.stack([np.stack([res.backward[b].paths[c][:, 0] for c in spec.cols], axis=1) for b in range(chains)])
+        traj[j], logev[j] = ref, res.log_evidence
+    return {c: traj[..., k].copy() for k, c in enumerate(spec.cols)}, logev
